@@ -6,12 +6,15 @@ with hg38's size and contig structure (3.1 Gb, 24 contigs, seed 20261002; no hum
 reads (143+150 after the 7-base trim) in barcodes of 100 pairs, streamed as batches of 10,000 barcodes = 1 M pairs.
 A "step" is ONE pass of the whole hot path (lariat.go:461-547 minus DumpToBams: SMEM seeding, SA lookup, chaining, banded
 SW extension, dedup/patch, mate rescue, region->CIGAR, tagBest/molecule inference/RFA/MAPQ/duplicates/split reads) over
-one batch; every step aligns a DIFFERENT batch; the default 50 steps are configs[2]'s 50 M pairs / 500 k barcodes.  All
-batches of the timed region are resident in HBM when it starts (lh_batch_upload_slot before, downloads after).
+one batch; every step aligns a DIFFERENT batch up to configs[2]'s 50 M pairs / 500 k barcodes (the default 25 steps of 2 M
+pairs), and longer runs align those batches again in turn.  All batches of the timed region are resident in HBM when it
+starts (lh_batch_upload_slot before, downloads after).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
       N > 1 without WORLD_SIZE in the environment: spawns `python -m torch.distributed.run --nproc-per-node N bench.py ...`
       (one fresh process per GPU; this parent never touches HIP).  Under torch.distributed.run: one rank per GPU over RCCL.
+      A plain run measures the headline alone; --full adds the roofline, the CPU baseline and the other legs (single GPU).
+      --dump-outputs DIR: the last timed step's result (dump_outputs) for comparing two builds output for output.
 
 Multi-GPU: barcodes are independent (lariat.go:348-350), so rank r aligns its own contiguous range of the barcode-sorted
 input (global batches r*K .. r*K+K-1; --strong splits K batches over the ranks instead) with the index replicated in its
@@ -30,6 +33,7 @@ sys.path.insert(0, ROOT)
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_bench.json")   # HBM-side counters of this workload (tools/pmc_summary.py), per kernel
 K1_FLOOR_FILE = os.path.join(ROOT, "profiles", "r06_k1_request_floor.json")   # pass 1's request stream recorded and replayed without bookkeeping (tools/k1_trace.py)
 HBM_PEAK_GBPS = 8000.0
+CONFIG2_PAIRS = 50_000_000   # BASELINE.json configs[2]: 50 M pairs / 500 k barcodes
 
 
 def parse():
@@ -48,7 +52,10 @@ def parse():
     ap.add_argument("--strong", action="store_true", help="strong scaling: --steps batches in total, split over the ranks (default weak: --steps per rank)")
     ap.add_argument("--cpu-sample-barcodes", type=int, default=10000, help="barcodes of the first batch timed on the host cores (cpu_baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational PCIe-inclusive / ceiling measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the informational PCIe-inclusive / ceiling measurements")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the single-GPU run measures: roofline, cpu_baseline, host_to_host, end_to_end, pcie, "
+                                                        "two_lanes, index_from_files and the configs[4] legs (off: the run sets up, warms up, times --steps steps and prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (a fixed sample of its barcodes, every result field) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -118,14 +125,14 @@ def main():
     n_cpus = len(os.sched_getaffinity(0))
     host_threads = n_cpus if numa.get("bound") else max(1, n_cpus // max(1, world))   # host-side worker threads of this rank
     import numpy as np
-    import torch
     dist = None
     # LH_BENCH_SHARE_GPU=1 (development aid for 1-GPU boxes): all ranks use device 0 and the control collectives run over gloo,
     # which exercises everything of the N>1 path except RCCL itself
     share = os.environ.get("LH_BENCH_SHARE_GPU") == "1"
     if share:
         local_rank = 0
-    if world > 1:
+    if world > 1:   # torch serves the process group alone: a single rank does not import it (the library names its device and synchronises its own streams)
+        import torch
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local_rank)
@@ -133,8 +140,6 @@ def main():
             dist.init_process_group(backend="gloo")
         else:
             dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
-    elif torch.cuda.is_available():
-        torch.cuda.set_device(local_rank)
 
     from lariat_amd import capi, workload
     import __graft_entry__ as ge
@@ -170,19 +175,24 @@ def main():
     else:
         my_batches = list(range(rank * a.steps, (rank + 1) * a.steps))
     n_pairs = a.barcodes * a.pairs_per_barcode
+    # the distinct batches hold configs[2]'s 50 M pairs at most (25 batches at the defaults): later steps align them again in turn, as they do
+    # when HBM runs out first.  Synthesising a batch costs ~4 CPU-seconds, so this bounds the set-up of a long run
+    max_slots = max(1, -(-CONFIG2_PAIRS // n_pairs))
     ctx = idx.context(n_pairs, lanes=a.lanes)
     opts = lib.opts()
     t0 = time.time()
     first = None
     keep_reads = []
+    slot_bc_pair_off = []   # each resident batch's barcode boundaries (dump_outputs samples barcodes)
     n_slots = 0
-    for slot, g in enumerate(my_batches):
+    for slot, g in enumerate(my_batches[:max_slots]):
         if slot and lib.device_memory(local_rank)[0] < (16 << 30):   # leave room for the kernels' scratch: later steps reuse the resident batches in turn
             break
         r = lib.synth_reads(pac, l_pac, read_ctg, seed=workload.READS_SEED + g, n_barcodes=a.barcodes, pairs_per_barcode=a.pairs_per_barcode,
                             threads=host_threads)
         b = capi.Batch.from_arrays(r["seq"], r["seq_off"], r["bc_pair_off"], r["name_seed"])
         ctx.upload_slot(slot, b)
+        slot_bc_pair_off.append(np.asarray(r["bc_pair_off"]))
         n_slots = slot + 1
         if first is None:
             first = (r, b)
@@ -190,10 +200,9 @@ def main():
             keep_reads.append(r)   # host copies of a few batches: the host-to-host leg streams them through one context
     t_reads_upload = time.time() - t0
 
-    def sync_all():
+    def sync_all():   # (lh_batch_upload_slot and lh_align_resident return with their streams synchronised: a single rank has nothing to wait for)
         if dist is not None:
             dist.barrier()
-        if torch.cuda.is_available():
             torch.cuda.synchronize()
 
     for w in range(a.warmup):
@@ -233,6 +242,10 @@ def main():
         avg = {k: float(np.mean(v)) for k, v in kern.items()}
         res = ctx.download()   # the last batch's result: work counters of one step
         cnt = res.counters
+        dumped = None
+        if a.dump_outputs:   # the last step aligned the batch in slot (steps - 1) % n_slots
+            last = (len(my_batches) - 1) % n_slots
+            dumped = dict(dump_outputs(res, slot_bc_pair_off[last], a.dump_outputs), batch=my_batches[last])
         out = {
             "metric": "read-pairs/sec aligned to hg38 (per-barcode align loop: SMEM seeding + SW + RFA/MAPQ on device); synthetic hg38-scale reference",
             "value": round(value, 1), "unit": "read-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -246,7 +259,6 @@ def main():
                        "lanes_per_context": a.lanes, "distinct_batches_resident": n_slots,
                        "hbm_GiB": {"free_during_run": round(hbm_free / 2**30, 1), "total": round(hbm_total / 2**30, 1)},
                        "parallelism": "barcode-range shards, index replicated, no collective"},
-            "roofline": roofline(lib, idx, avg, cnt, first[0], local_rank, a),
             "kernel_ms_note": "HIP-event durations of the first lane's launches" + ((" (each launch = 1/%d of a batch; the other parts run beside it)" % a.lanes if a.lanes > 1 else "")),
             "kernel_ms": {k: round(v, 3) for k, v in avg.items()},
             "work_per_step": cnt,
@@ -254,17 +266,21 @@ def main():
         }
         if per_rank:
             out["per_rank"] = per_rank
+        if dumped:
+            out["outputs"] = dumped
+        if a.full:
+            out["roofline"] = roofline(lib, idx, avg, cnt, first[0], local_rank, a)
         ctx.close()   # its pools and the resident batches (~70 GB next to the 131 GB index) make room for the other legs
-        if not a.no_extras and world == 1:   # the other legs and the CPU baseline: on the single-GPU run only
+        if a.full and not a.no_extras and world == 1:   # the other legs and the CPU baseline: on the single-GPU run only
             out["host_to_host"] = host_to_host(lib, idx, keep_reads, n_pairs, opts)
             try:
                 out["end_to_end"] = end_to_end(lib, idx, a, pac, l_pac, ctg, opts, local_rank)
             except Exception as e:   # (informational leg: a full tmp directory must not cost the headline line)
                 out["end_to_end"] = {"failed": "%s: %s" % (type(e).__name__, e)}
             out.update(extras(lib, idx, first[1], n_pairs, opts, elapsed / max(1, len(my_batches))))
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a, idx, pac, first[0])
-        if not a.no_extras and world == 1:
+        if a.full and not a.no_extras and world == 1:
             try:   # the reference's own way to an index: bwa_idx_load from `bwa index`'s files (gobwa.go:128-147) — this index saved in that layout, loaded again
                 out["setup_s"].update(index_from_files(lib, idx, local_rank))
             except Exception as e:
@@ -281,6 +297,50 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20261016
+DUMP_PAIRS = 20000        # pairs of the sampled barcodes: 200 of the headline's 100-pair barcodes, ~20 MB of float64
+DUMP_BYTES = 60 << 20     # at most this much data in all (the .npy headers add a few kB)
+
+
+def dump_outputs(res, bc_pair_off, d):
+    """what the timed path handed back in its last step, to compare two builds output for output: every field of the lh_result of a fixed,
+    seeded sample of the batch's barcodes (the same barcodes for the same arguments), as float64 .npy files under d (exact for every integer
+    field: positions and indices stay below 2^53).  Per-read fields hold the sampled barcodes' reads in order, per-candidate fields their
+    candidates; cand_off, cigar_off and mm_off are rebased to the sample, while mate_idx, active_idx, second_best_idx and split_idx keep the
+    batch's numbering.  The work counters are left out: they count what a build did, not what it computed.  Barcodes are taken in the
+    sample's order while their data fits DUMP_BYTES.  Returns what was written, for the result line."""
+    import numpy as np
+    from lariat_amd import capi
+    bco = np.asarray(bc_pair_off, dtype=np.int64)
+    order = np.random.default_rng(DUMP_SEED).permutation(len(bco) - 1)
+    order = order[: max(1, int(np.searchsorted(np.cumsum(np.diff(bco)[order]), DUMP_PAIRS, side="right")))]
+    r0, r1 = 2 * bco[order], 2 * bco[order + 1]                  # the barcodes' reads, and below their candidates, CIGAR words and mismatch loci
+    c0, c1 = res.cand_off[r0], res.cand_off[r1]
+    nbytes = 8 * ((r1 - r0) * 9 + (c1 - c0) * 30 + (res.cigar_off[c1] - res.cigar_off[c0]) + 2 * (res.mm_off[c1] - res.mm_off[c0]))
+    keep = np.sort(order[: max(1, int(np.searchsorted(np.cumsum(nbytes), DUMP_BYTES, side="right")))])
+
+    def ranges(lo, hi):
+        return np.concatenate([np.arange(s, e, dtype=np.int64) for s, e in zip(lo, hi)])
+
+    def rebased(off, idx):
+        return np.concatenate([[0], np.cumsum(off[idx + 1] - off[idx])])
+
+    k0, k1 = res.cand_off[2 * bco[keep]], res.cand_off[2 * bco[keep + 1]]
+    reads = ranges(2 * bco[keep], 2 * bco[keep + 1])
+    cands = ranges(k0, k1)
+    mm = ranges(res.mm_off[k0], res.mm_off[k1])
+    out = {"sample_barcodes": keep, "cand_off": rebased(res.cand_off, reads), "cigar_off": rebased(res.cigar_off, cands), "mm_off": rebased(res.mm_off, cands),
+           "cigar": res.cigar[ranges(res.cigar_off[k0], res.cigar_off[k1])], "mm_ref_loc": res.mm_ref_loc[mm], "mm_read_loc": res.mm_read_loc[mm]}
+    for n, _, _ in capi._RESULT_CAND_FIELDS + capi._RESULT_INF_FIELDS + [("log_alignment_probability", None, None)]:
+        out[n] = getattr(res, n)[cands]
+    for n, _, _ in capi._RESULT_READ_FIELDS:
+        out[n] = getattr(res, n)[reads]
+    os.makedirs(d, exist_ok=True)
+    for n, v in out.items():
+        np.save(os.path.join(d, n + ".npy"), np.asarray(v, dtype=np.float64))
+    return {"dir": d, "barcodes": len(keep), "reads": len(reads), "candidates": len(cands), "bytes": int(sum(8 * len(v) for v in out.values()))}
 
 
 def roofline(lib, idx, avg, cnt, reads, device, a):

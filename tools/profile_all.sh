@@ -6,7 +6,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/prof_r06
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $REPO/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python3 $REPO/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/kt -- $CMD > $OUT/kt.log 2>&1
 rocprofv3 --pmc FETCH_SIZE TCC_HIT_sum --output-format csv -d $OUT/p1 -- $CMD > $OUT/p1.log 2>&1
 rocprofv3 --pmc WRITE_SIZE TCC_MISS_sum --output-format csv -d $OUT/p2 -- $CMD > $OUT/p2.log 2>&1
@@ -14,7 +14,7 @@ rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_
 cd $REPO
 DB=$(find $OUT/kt -name "*.db" | head -1)
 python3 tools/rocpd_stats.py $DB 0.05 > $OUT/kernel_stats.csv
-python3 tools/pmc_summary.py --out $OUT/pmc.json --commit $1 --command "rocprofv3 --pmc {FETCH_SIZE TCC_HIT_sum | WRITE_SIZE TCC_MISS_sum | SQ_*} --output-format csv -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extras (one pipeline, 2 M-pair batches: 5 dispatches of each hot-path kernel = 1 warm-up + 4 steps; one pass per counter group)" --ceiling 50.5 --note "ceiling = independent random 32-B reads from a 3 GiB table (hg38 occurrence table); 36.8 G/s from a 48 GiB table (dense SA / ISA): profiles/r02_random_read_ceiling.log" $(find $OUT/p1 $OUT/p2 $OUT/p3 -name "*counter_collection.csv")
+python3 tools/pmc_summary.py --out $OUT/pmc.json --commit $1 --command "rocprofv3 --pmc {FETCH_SIZE TCC_HIT_sum | WRITE_SIZE TCC_MISS_sum | SQ_*} --output-format csv -- python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-extras (one pipeline, 2 M-pair batches: 5 dispatches of each hot-path kernel = 1 warm-up + 4 steps; one pass per counter group)" --ceiling 50.5 --note "ceiling = independent random 32-B reads from a 3 GiB table (hg38 occurrence table); 36.8 G/s from a 48 GiB table (dense SA / ISA): profiles/r02_random_read_ceiling.log" $(find $OUT/p1 $OUT/p2 $OUT/p3 -name "*counter_collection.csv")
 grep "^{" $OUT/kt.log | tail -n 1 > $OUT/kt_bench.json
 rm -rf $OUT/kt $OUT/p1 $OUT/p2 $OUT/p3
 ls -la $OUT
