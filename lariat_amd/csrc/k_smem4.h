@@ -24,15 +24,28 @@
 //  - SWEEP FILTER, K-MER TREE TABLE, COLLAPSED SWEEPS, FORWARD JUMP, PASS-2 PROBE, PASS 3 BY TEXT: see the blocks below.
 //
 //  - query: 4-bit packed in LDS (8 bases per word, word w of lane L at qn[w*64+L]), staged by the whole wave
-//  - prev/curr interval lists: 16-B packed entries in an HBM slab interleaved by thread; the entry the next row starts with stays in
-//    registers (and is never written to the slab: most backward rows have a single survivor) and the following one is prefetched
-//    while the current extension is in flight
+//  - prev/curr interval lists: 16-B packed entries; the entry the next row starts with stays in registers (and is never stored: most
+//    backward rows have a single survivor) and the following one is prefetched while the current extension is in flight.  The first
+//    LH_K1_RING stored entries of each list are kept in LDS beside the query, the rest in an HBM slab interleaved by thread (see LIST_PUT)
 #pragma once
 #ifndef LH_K1_SLAB_CHUNK
 #define LH_K1_SLAB_CHUNK 4   // entries of a lane's interval list that share a 64-B line of the slab (1: the r02-r05 layout); must divide LH_MAXLEN + 2
 #endif
 #include "lh_dev.h"
 static_assert((LH_MAXLEN + 2) % LH_K1_SLAB_CHUNK == 0, "a lane's list of LH_MAXLEN + 2 entries is a whole number of chunks");
+// LDS of a pass-1 / pass-2 block (one wave): the query, QW words per lane, and the ring, 2 lists x R entries x 16 B per lane.  At LH_SMEM4_WAVES = 4 waves per
+// SIMD a CU holds 16 such blocks in its 160 KiB: 10 KiB each.  The full query (LH_MAXLEN bases: 32 words) leaves room for one entry per list; the
+// instance for batches whose reads have at most 8 * LH_K1_QW_SMALL bases (the host picks it) for two.  -DLH_K1_RING=n fixes the ring at n entries.
+#define LH_K1_LDS_BUDGET 10240
+#ifndef LH_K1_QW_SMALL
+#define LH_K1_QW_SMALL 24
+#endif
+#ifdef LH_K1_RING
+#define LH_K1_RING_OF(qw_) (LH_K1_RING)
+#else
+#define LH_K1_RING_OF(qw_) ((LH_K1_LDS_BUDGET - (qw_) * 256) / 2048)
+#endif
+static_assert(LH_K1_QW_SMALL >= 1 && LH_K1_QW_SMALL <= 32, "the small query staging holds at most the full query");
 
 struct __attribute__((aligned(16))) PEnt { u64 lo, hi; };   // x0:40 | x2[0..23]  /  x1:40 | x2[24..32] | info:15
 #define LH_M40 0xffffffffffull
@@ -231,6 +244,16 @@ struct K1Big { const int32_t* list; const int32_t* count; const int32_t* slot; D
 __device__ u64* lh_k1_trace;            // null: tracing off
 __device__ uint32_t lh_k1_trace_cap;    // entries per lane
 __device__ uint32_t* lh_k1_trace_n;     // [T] requests of lane t (may exceed the cap: the rest was not recorded)
+// list lengths, passes 1 and 2 (not BIG): lh_k1_lens[((pass - 1) * 3 + kind) * 64 + min(v, 63)], kind 0: ncurr at a push (the stored position is ncurr in a
+// forward list, ncurr - 1 in a backward row), 1: nprev at a sweep's read of a stored entry, 2: the stored position that read takes
+#define K1L_PUSH 0
+#define K1L_NPREV 1
+#define K1L_READ 2
+__device__ unsigned long long* lh_k1_lens;
+#define K1_LEN(kind_, v_)                                                                                                                        \
+    {                                                                                                                                            \
+        if (DO12 && !BIG && lh_k1_lens) { const int v__ = (v_); atomicAdd(&lh_k1_lens[((PASS - 1) * 3 + (kind_)) * 64 + (v__ < 63 ? v__ : 63)], 1ull); } \
+    }
 #define K1_REQ(tab_, ptr_, bytes_)                                                                                                              \
     {                                                                                                                                            \
         if (PASS == 1 && !BIG && lh_k1_trace) {                                                                                                  \
@@ -240,16 +263,25 @@ __device__ uint32_t* lh_k1_trace_n;     // [T] requests of lane t (may exceed th
     }
 #else
 #define K1_REQ(tab_, ptr_, bytes_)
+#define K1_LEN(kind_, v_)
 #endif
 
-template <int PASS, bool BIG>
+template <int PASS, bool BIG, int QW = 32>
 __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pass(DIndex ix, DOpts o, int n_reads_all, const uint8_t* __restrict__ seq, const i64* __restrict__ seq_off,
                                                DIntv* __restrict__ intv_out, int32_t* __restrict__ n_intv, int32_t* __restrict__ status, PEnt* __restrict__ slab,
                                                int32_t* __restrict__ next_read, DCounters* __restrict__ ctr, K1Big big) {
     const int n_reads = (BIG || big.list) ? *big.count : n_reads_all;
     constexpr int ICAP = BIG ? LH_BIG_INTV : LH_MAX_INTV;
-    __shared__ uint32_t qn[32 * 64];
     constexpr bool DO1 = PASS == 1, DO2 = PASS == 2, DO12 = DO1 || DO2, DO3 = PASS == 3, P3T = PASS == 3;
+    static_assert(QW >= 1 && QW <= 32, "query staging: 1 to 32 words per lane");
+    constexpr int R = DO12 ? LH_K1_RING_OF(QW) : 0;   // stored entries of each list kept in LDS
+    static_assert(R >= 0, "ring size");
+#ifndef LH_K1_RING
+    static_assert(!DO12 || QW * 256 + R * 2048 <= LH_K1_LDS_BUDGET, "query + ring within the LDS of a block at LH_SMEM4_WAVES waves per SIMD");
+#endif
+    // the query, then the ring: word k of entry p < R of list A at qn[(QW + 4 * p + k) * 64 + lane], of list B at qn[(QW + 4 * (R + p) + k) * 64 + lane]
+    // (one array and four planes of words, as the query: every access is off the same per-lane address)
+    __shared__ uint32_t qn[(QW + 8 * R) * 64];
     // PASS 2 BY TASKS (r05).  A read's re-seeding calls — one bwt_smem1 from the middle of each long, rare SMEM — are independent of each other, and on repeat
     // families a single call sweeps a forward list of dozens of entries over a hundred rows: a read with ten of them kept its lane for tens of milliseconds
     // after every other lane had finished.  With a task list (k_p2_tasks: big.list / big.count) a read's calls are dealt out to up to LH_P2_SPLIT lanes; what
@@ -350,8 +382,8 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
 #define Q8(s_, out_)                                                                                         \
     {                                                                                                        \
         int w_ = (s_) >> 3, sh_ = ((s_) & 7) * 4;                                                            \
-        uint32_t lo_ = (w_ >= 0 && w_ < 32) ? qn[w_ * 64 + lane] : 0x44444444u;                              \
-        uint32_t hi_ = (w_ + 1 >= 0 && w_ + 1 < 32) ? qn[(w_ + 1) * 64 + lane] : 0x44444444u;                \
+        uint32_t lo_ = (w_ >= 0 && w_ < QW) ? qn[w_ * 64 + lane] : 0x44444444u;                              \
+        uint32_t hi_ = (w_ + 1 >= 0 && w_ + 1 < QW) ? qn[(w_ + 1) * 64 + lane] : 0x44444444u;                \
         out_ = sh_ ? (lo_ >> sh_) | (hi_ << (32 - sh_)) : lo_;                                               \
     }
     // issue the reads of the sixteen text bases from position p_ on (p_ >= -16); T16_A() / T16_B() assemble the first / the second
@@ -363,6 +395,27 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
 #define PREV ((rflags & RF_CURA) ? LB : LA)
 #define K1_SLAB_IX(e_) (((uint32_t)(e_) / LH_K1_SLAB_CHUNK) * (LH_K1_SLAB_CHUNK * T) + ((uint32_t)(e_) % LH_K1_SLAB_CHUNK))
 #define PREV_AT(e_) PREV[K1_SLAB_IX(e_)]
+    // A list's STORED entries are numbered from 0: a forward list stores its entries 0 .. n - 2 at p = e (the last one is ce), a backward row
+    // its entries 1 .. n - 1 at p = e - 1 (the first one is ce).  p < R: the lane's ring in LDS, else the slab (the overflow, as before)
+#define RING_W(a_, p_) (&qn[(QW + 4 * (((a_) ? 0 : R) + (p_))) * 64 + lane])
+#define LIST_PUT(p_, e_)                                                                                     \
+    {                                                                                                        \
+        const int p__ = (p_);                                                                                \
+        K1_LEN(K1L_PUSH, ncurr)                                                                              \
+        if ((unsigned)p__ < (unsigned)R) {                                                                   \
+            uint32_t* w_ = RING_W(rflags & RF_CURA, p__);                                                    \
+            w_[0] = (uint32_t)(e_).lo; w_[64] = (uint32_t)((e_).lo >> 32); w_[128] = (uint32_t)(e_).hi; w_[192] = (uint32_t)((e_).hi >> 32); \
+        } else { CURR[K1_SLAB_IX(p__)] = (e_); K1_REQ(K1T_SLAB_W, &CURR[K1_SLAB_IX(p__)], 16) }              \
+    }
+#define LIST_GET(p_, out_)                                                                                   \
+    {                                                                                                        \
+        const int p__ = (p_);                                                                                \
+        K1_LEN(K1L_NPREV, nprev) K1_LEN(K1L_READ, p__)                                                       \
+        if ((unsigned)p__ < (unsigned)R) {                                                                   \
+            const uint32_t* w_ = RING_W(!(rflags & RF_CURA), p__);                                           \
+            out_.lo = (u64)w_[0] | (u64)w_[64] << 32; out_.hi = (u64)w_[128] | (u64)w_[192] << 32;           \
+        } else { out_ = PREV_AT(p__); K1_REQ(K1T_SLAB_R, &PREV_AT(p__), 16) }                                \
+    }
     // forward extension: the next base decides between another bwt_extend and the end of the forward list
 #define FWD_ADVANCE()                                                                                        \
     {                                                                                                        \
@@ -490,7 +543,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
         else if (by_text && (rflags & (RF_REV | RF_TRIF)) == RF_REV && nprev > 1 && c2 == 1 && min_intv == 1) { rflags |= RF_TRI; st = S4_BRUN_INIT; } \
         else {                                                                                               \
             ec = c_; st = S4_REQ_BWD;                                                                        \
-            if (nprev > 1) { pn = PREV_AT((rflags & RF_REV) ? nprev - 2 : 1); K1_REQ(K1T_SLAB_R, &PREV_AT((rflags & RF_REV) ? nprev - 2 : 1), 16) }                                                \
+            if (nprev > 1) LIST_GET((rflags & RF_REV) ? nprev - 2 : 0, pn)                                  \
             if (ktl) CODE16(i, rcode)                                                                        \
         }                                                                                                    \
     }
@@ -501,7 +554,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
         if (j < nprev) {                                                                                     \
             c0 = PE_X0(pn); c1 = PE_X1(pn); c2 = PE_X2(pn); cinfo = PE_INFO(pn);                             \
             st = S4_REQ_BWD;                                                                                 \
-            if (j + 1 < nprev) { pn = PREV_AT((rflags & RF_REV) ? nprev - 2 - j : j + 1); K1_REQ(K1T_SLAB_R, &PREV_AT((rflags & RF_REV) ? nprev - 2 - j : j + 1), 16) }                                    \
+            if (j + 1 < nprev) LIST_GET((rflags & RF_REV) ? nprev - 2 - j : j, pn)                           \
         } else if (ncurr == 0) st = S4_SMEM_DONE;                                                            \
         else {                                                                                               \
             nprev = ncurr; --i;                                                                              \
@@ -540,7 +593,11 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             i64 off = 0;
             int ln = 0, rr = -1;
             if (st == S4_FETCH) {
+#ifdef LH_EMU
                 int idx = chunk_next + lanes_below(need, lane);
+#else
+                int idx = chunk_next + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));   // (lanes_below without a per-lane mask kept across the loop)
+#endif
                 rr = idx < chunk_end ? idx : newbase + (idx - chunk_end);
                 if (rr >= n_reads) st = S4_DONE;
                 else {
@@ -575,7 +632,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
                         nb16 |= v << (4 * b);
                     }
                     uint32_t other = __shfl_xor(nb16, 1);
-                    if (!(lane & 1)) qn[(lane >> 1) * 64 + Lk[k]] = nb16 | other << 16;
+                    if (!(lane & 1) && (lane >> 1) < QW) qn[(lane >> 1) * 64 + Lk[k]] = nb16 | other << 16;   // (words past QW: past the batch's longest read)
                 }
             }
             if (st == S4_FETCH) {
@@ -943,7 +1000,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             if (ok.x2 != c2) {
                 ce = pe_pack(c0, c1, c2, cinfo);
                 if (ok.x2 < (u64)min_intv) { st = S4_BWD_INIT; ncurr++; }   // the interval is too small to be extended further: ce is the list's last entry
-                else if (FWD_PUSH_OK()) { if (!ncurr) emin = cinfo; CURR[K1_SLAB_IX(ncurr)] = ce; K1_REQ(K1T_SLAB_W, &CURR[K1_SLAB_IX(ncurr)], 16) ncurr++; }
+                else if (FWD_PUSH_OK()) { if (!ncurr) emin = cinfo; LIST_PUT(ncurr, ce) ncurr++; }
             }
             if (st == S4_REQ_FWD) {
                 c0 = ok.x0; c1 = ok.x1; c2 = ok.x2; cinfo = i + 1; ++i;
@@ -957,7 +1014,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             } else if (ncurr == 0 || ok.x2 != last_size) {
                 PEnt e = pe_pack(ok.x0, ok.x1, ok.x2, cinfo);
                 if (ncurr == 0) ce = e;   // a row's first entry is only ever read through ce
-                else { CURR[K1_SLAB_IX(ncurr)] = e; K1_REQ(K1T_SLAB_W, &CURR[K1_SLAB_IX(ncurr)], 16) }
+                else LIST_PUT(ncurr - 1, e)
                 ncurr++;
                 last_size = ok.x2;
             }
@@ -1023,6 +1080,9 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
 #undef CURR
 #undef PREV
 #undef PREV_AT
+#undef RING_W
+#undef LIST_PUT
+#undef LIST_GET
 #undef K1_SLAB_IX
 #undef P3_NOTEXT
 #undef US0
@@ -1091,6 +1151,19 @@ __global__ void __launch_bounds__(64, LH_SMEM4_WAVES) k_k1_replay(const u64* __r
         }
     }
     if (acc == 0x9e3779b97f4a7c15ull) *sink = acc;
+}
+// a replay without some tables: each lane's sequence loses the requests of the tables in skip_mask (bit = K1T_*), in place, order kept.  Applied
+// with growing masks, one after the other (what an earlier mask removed is gone)
+__global__ void __launch_bounds__(256) k_k1_trace_skip(u64* __restrict__ trace, uint32_t* __restrict__ n_req, uint32_t cap, uint32_t T, uint32_t skip_mask) {
+    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < T; t += gridDim.x * blockDim.x) {
+        uint32_t n = n_req[t], w = 0;
+        if (n > cap) n = cap;
+        for (uint32_t k = 0; k < n; ++k) {
+            const u64 e = trace[(size_t)k * T + t];
+            if (!((skip_mask >> (int)(e >> 56)) & 1u)) trace[(size_t)(w++) * T + t] = e;
+        }
+        n_req[t] = w;
+    }
 }
 // requests and bytes per table
 __global__ void __launch_bounds__(256) k_k1_trace_hist(const u64* __restrict__ trace, const uint32_t* __restrict__ n_req, uint32_t cap, uint32_t T, unsigned long long* __restrict__ hist) {

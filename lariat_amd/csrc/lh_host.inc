@@ -97,6 +97,7 @@ struct lh_context {
     uint8_t* d_seq = nullptr; i64* d_seq_off = nullptr; u64* d_name_seed = nullptr; int32_t* d_bc_pair_off = nullptr; uint8_t* d_bc_do_rfa = nullptr;
     i64 *d_cen_start = nullptr, *d_cen_end = nullptr;
     int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false; i64 n_bases = 0; const uint32_t* q4 = nullptr;
+    int max_len = LH_MAXLEN;   // the selected batch's longest read (K1 stages its queries in that many bases' worth of LDS)
     // K1
     DIntv* d_intv = nullptr; DIntv* d_big_slab = nullptr; int32_t *d_big_slot = nullptr, *d_big_list = nullptr, *d_big_count = nullptr; int big_cap = 0, big_base = 0;   // reads with more than LH_MAX_INTV intervals (k_smem4.h BIG)
     K1Resume* d_k1_resume = nullptr; int32_t *d_k1_todo = nullptr, *d_p2_tasks = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read[6])
@@ -119,7 +120,7 @@ struct lh_context {
     struct DevBatch {
         uint8_t* seq = nullptr; i64* seq_off = nullptr; u64* name_seed = nullptr; int32_t* bc_pair_off = nullptr; uint8_t* bc_do_rfa = nullptr;
         i64 *cen_start = nullptr, *cen_end = nullptr;
-        int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false, filled = false; i64 n_bases = 0;
+        int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false, filled = false; i64 n_bases = 0; int max_len = LH_MAXLEN;
         i64 cap_bases = 0; int cap_reads = 0, cap_bc = 0;   // what the slot's own buffers hold (slots > 0)
     };
     std::vector<DevBatch> slots; std::mutex slot_mu;   // slot_mu: slots' size and `filled`, sel_slot / resident, free_later
@@ -314,7 +315,7 @@ static void pipe_free(lh_context* c) {
 static void select_slot(lh_context* c, const lh_context::DevBatch& sl) {
     c->d_seq = sl.seq; c->d_seq_off = sl.seq_off; c->d_name_seed = sl.name_seed; c->d_bc_pair_off = sl.bc_pair_off; c->d_bc_do_rfa = sl.bc_do_rfa;
     c->d_cen_start = sl.cen_start; c->d_cen_end = sl.cen_end;
-    c->n_pairs = sl.n_pairs; c->n_reads = sl.n_reads; c->n_bc = sl.n_bc; c->has_cen = sl.has_cen; c->n_bases = sl.n_bases;
+    c->n_pairs = sl.n_pairs; c->n_reads = sl.n_reads; c->n_bc = sl.n_bc; c->has_cen = sl.has_cen; c->n_bases = sl.n_bases; c->max_len = sl.max_len;
 }
 
 static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool staged) {
@@ -329,10 +330,12 @@ static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool
     i64 nb = b->seq_off[n_reads];
     if (nb > c->cap_bases) return set_err(LH_E_CAPACITY, "too many bases for the context");
     if (b->seq_off[0] != 0) return set_err(LH_E_ARG, "seq_off must start at 0");
+    i64 lmax = 0;
     for (int r = 0; r < n_reads; ++r) {
         i64 l = b->seq_off[r + 1] - b->seq_off[r];
         if (l < 0) return set_err(LH_E_ARG, "seq_off must be non-decreasing (read " + std::to_string(r) + ")");
         if (l > LH_MAX_READ_LEN) return set_err(LH_E_LIMIT, "read " + std::to_string(r) + " is longer than LH_MAX_READ_LEN");
+        lmax = l > lmax ? l : lmax;
     }
     for (int k = 0; k < b->n_barcodes; ++k)
         if (b->bc_pair_off[k + 1] < b->bc_pair_off[k]) return set_err(LH_E_ARG, "bc_pair_off must be non-decreasing (barcode " + std::to_string(k) + ")");
@@ -358,7 +361,7 @@ static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool
         DALLOC(sl.seq, (size_t)sl.cap_bases + 64); DALLOC(sl.seq_off, (size_t)n_reads + 1); DALLOC(sl.name_seed, (size_t)b->n_pairs);
         DALLOC(sl.bc_pair_off, (size_t)b->n_barcodes + 1); DALLOC(sl.bc_do_rfa, (size_t)b->n_barcodes); DALLOC(sl.cen_start, nc); DALLOC(sl.cen_end, nc);
     }
-    sl.n_pairs = b->n_pairs; sl.n_reads = n_reads; sl.n_bc = b->n_barcodes; sl.n_bases = nb;
+    sl.n_pairs = b->n_pairs; sl.n_reads = n_reads; sl.n_bc = b->n_barcodes; sl.n_bases = nb; sl.max_len = (int)lmax;
     HIPCHK(hipMemcpyAsync(sl.seq, b->seq, (size_t)nb, hipMemcpyHostToDevice, us));
     HIPCHK(hipMemcpyAsync(sl.seq_off, b->seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, us));
     std::vector<u64> seeds;
@@ -466,17 +469,23 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         LH_LAUNCH(k_smem_first, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_k1_resume, c->d_k1_todo, c->d_next_read + 6, c->d_ctr);
 #ifdef LH_K1_TRACE
         u64* d_trace = nullptr; uint32_t* d_trace_n = nullptr; const uint32_t trace_cap = 4096;
+        unsigned long long* d_lens = nullptr;   // list lengths, passes 1 and 2 (k_smem4.h: K1_LEN)
         const bool tracing = getenv("LH_K1_TRACE") != nullptr;
         if (tracing) {
             const size_t Tl = (size_t)g4 * 64;
-            DALLOC(d_trace, Tl * trace_cap); DALLOC(d_trace_n, Tl);
+            DALLOC(d_trace, Tl * trace_cap); DALLOC(d_trace_n, Tl); DALLOC(d_lens, 2 * 3 * 64);
             HIPCHK(hipMemsetAsync(d_trace_n, 0, Tl * 4, c->stream));
+            HIPCHK(hipMemsetAsync(d_lens, 0, 2 * 3 * 64 * 8, c->stream));
+            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_lens), &d_lens, sizeof d_lens, 0, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace), &d_trace, sizeof d_trace, 0, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace_cap), &trace_cap, sizeof trace_cap, 0, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace_n), &d_trace_n, sizeof d_trace_n, 0, hipMemcpyHostToDevice, c->stream));
         }
 #endif
-        LH_LAUNCH((k_smem_pass<1, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read, c->d_ctr, first);
+        // the instance whose query staging holds the batch's longest read: the LDS it leaves is the lists' ring (k_smem4.h: LH_K1_QW_SMALL)
+        const bool qw_small = c->max_len <= 8 * LH_K1_QW_SMALL;
+        if (qw_small) LH_LAUNCH((k_smem_pass<1, false, LH_K1_QW_SMALL>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read, c->d_ctr, first);
+        else LH_LAUNCH((k_smem_pass<1, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read, c->d_ctr, first);
         T_END();
 #ifdef LH_K1_TRACE
         if (tracing) {   // the request stream's own floor: the same sequences, the same geometry, nothing in between (tools/k1_trace.py reads the line)
@@ -487,24 +496,43 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
             HIPCHK(hipMemsetAsync(d_hist, 0, (2 * K1T_N + 2) * 8, c->stream));
             hipEvent_t e0, e1;
             HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+            auto replay = [&](float& best, float& sum) -> int {
+                best = 1e30f; sum = 0;
+                for (int rep_ = 0; rep_ < 4; ++rep_) {
+                    HIPCHK(hipEventRecord(e0, c->stream));
+                    LH_LAUNCH(k_k1_replay, g4, 64, c->stream, (const u64*)d_trace, (const uint32_t*)d_trace_n, trace_cap, d_sink);
+                    HIPCHK(hipEventRecord(e1, c->stream));
+                    HIPCHK(hipEventSynchronize(e1));
+                    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+                    if (rep_) { sum += ms; best = ms < best ? ms : best; }   // (the first launch warms the trace's pages)
+                }
+                return LH_OK;
+            };
             float best = 1e30f, sum = 0;
-            for (int rep_ = 0; rep_ < 4; ++rep_) {
-                HIPCHK(hipEventRecord(e0, c->stream));
-                LH_LAUNCH(k_k1_replay, g4, 64, c->stream, (const u64*)d_trace, (const uint32_t*)d_trace_n, trace_cap, d_sink);
-                HIPCHK(hipEventRecord(e1, c->stream));
-                HIPCHK(hipEventSynchronize(e1));
-                float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-                if (rep_) { sum += ms; best = ms < best ? ms : best; }   // (the first launch warms the trace's pages)
-            }
+            { int rc = replay(best, sum); if (rc) return rc; }
             LH_LAUNCH(k_k1_trace_hist, 2048, 256, c->stream, (const u64*)d_trace, (const uint32_t*)d_trace_n, trace_cap, (uint32_t)(g4 * 64), d_hist);
             unsigned long long h[2 * K1T_N + 2];
             HIPCHK(hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
+            // LH_K1_REPLAY_SKIP = masks of tables (bit = K1T_*) separated by commas, each a superset of the one before: the replay again without them
+            std::string skip_js;
+            if (const char* sk = getenv("LH_K1_REPLAY_SKIP")) {
+                for (const char* q = sk; *q;) {
+                    char* end = nullptr;
+                    const unsigned long m = strtoul(q, &end, 0);
+                    if (end == q) break;
+                    LH_LAUNCH(k_k1_trace_skip, 2048, 256, c->stream, d_trace, d_trace_n, trace_cap, (uint32_t)(g4 * 64), (uint32_t)m);
+                    float b_ = 0, s_ = 0;
+                    { int rc = replay(b_, s_); if (rc) return rc; }
+                    skip_js += std::string(skip_js.empty() ? "" : ", ") + "{\"skip_mask\": " + std::to_string(m) + ", \"replay_ms_avg\": " + std::to_string(s_ / 3) + ", \"replay_ms_min\": " + std::to_string(b_) + "}";
+                    q = *end == ',' ? end + 1 : end;
+                }
+            }
             static const char* const tn[K1T_N] = {"occurrence", "tree", "bloom1", "bloom2", "rep_t", "plcp", "text", "sa", "isa", "interval_slab_read", "interval_slab_write", "interval_out_write", "reads"};
             std::string js = "{\"pairs\": " + std::to_string(N / 2) + ", \"lanes\": " + std::to_string((long long)g4 * 64) + ", \"replay_ms_avg\": " + std::to_string(sum / 3) + ", \"replay_ms_min\": " + std::to_string(best) +
                              ", \"dropped_requests\": " + std::to_string(h[2 * K1T_N]) + ", \"requests_by_table\": {";
             for (int i = 0; i < K1T_N; ++i) js += std::string(i ? ", " : "") + "\"" + tn[i] + "\": [" + std::to_string(h[2 * i]) + ", " + std::to_string(h[2 * i + 1]) + "]";
-            js += "}}";
+            js += "}, \"replay_without\": [" + skip_js + "]}";
             fprintf(stderr, "[lh] K1TRACE %s\n", js.c_str());
             hipEventDestroy(e0); hipEventDestroy(e1);
             hipFree(d_trace); hipFree(d_trace_n); hipFree(d_sink); hipFree(d_hist);
@@ -518,11 +546,34 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         if (p2_tasks) {
             K1Big p2 = nobig; p2.list = c->d_p2_tasks; p2.count = c->d_next_read + 7; p2.slot = c->d_k1_todo;   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
             LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, c->d_next_read + 7, c->d_k1_todo);
-            LH_LAUNCH((k_smem_pass<2, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, p2);
+            if (qw_small) LH_LAUNCH((k_smem_pass<2, false, LH_K1_QW_SMALL>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, p2);
+            else LH_LAUNCH((k_smem_pass<2, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, p2);
             LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
-        } else
+        } else if (qw_small)
+        LH_LAUNCH((k_smem_pass<2, false, LH_K1_QW_SMALL>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, nobig);
+        else
         LH_LAUNCH((k_smem_pass<2, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, nobig);
         T_END();
+#ifdef LH_K1_TRACE
+        if (tracing) {   // the list lengths of passes 1 and 2 (tools/k1_trace.py reads the line)
+            unsigned long long* nul = nullptr;
+            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_lens), &nul, sizeof nul, 0, hipMemcpyHostToDevice, c->stream));
+            unsigned long long hl[2 * 3 * 64];
+            HIPCHK(hipMemcpyAsync(hl, d_lens, sizeof hl, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            static const char* const kn[3] = {"ncurr_at_push", "nprev_at_read", "stored_position_read"};
+            std::string js = "{";
+            for (int ps = 0; ps < 2; ++ps)
+                for (int k = 0; k < 3; ++k) {
+                    js += std::string(ps || k ? ", " : "") + "\"pass" + std::to_string(ps + 1) + "_" + kn[k] + "\": [";
+                    for (int v = 0; v < 64; ++v) js += std::string(v ? ", " : "") + std::to_string(hl[(ps * 3 + k) * 64 + v]);
+                    js += "]";
+                }
+            js += "}";
+            fprintf(stderr, "[lh] K1LENS %s\n", js.c_str());
+            hipFree(d_lens);
+        }
+#endif
         T_BEGIN("k_smem4_p3");
         if (o.max_mem_intv > 0 && q4)   // forward-only walks: one thread per read, in lockstep
             LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr);

@@ -3,7 +3,9 @@
 k_smem_pass<1> records every memory request it makes (table, address, bytes; k_smem4.h: K1_REQ) while it aligns one headline batch (BASELINE configs[2]: 2 M
 pairs against the hg38-scale index), and k_k1_replay then issues exactly those sequences with the same launch geometry and no bookkeeping in between: its
 time is the floor of THIS request stream on this chip.  Prints one JSON object (-> profiles/r05_k1_request_floor.json, which bench.py's roofline reads):
-requests and bytes per table, the replay's time, pass 1's own time from the product build on the same batch."""
+requests and bytes per table, the replay's time, pass 1's own time from the product build on the same batch.
+--skip TABLE,TABLE (repeatable; each adds to the tables left out before it) replays the stream again without those tables' requests: the floor a
+change that removes them could reach at most.  The trace build also counts the interval lists' lengths in passes 1 and 2 (k_smem4.h: K1_LEN)."""
 import argparse
 import json
 import os
@@ -11,6 +13,8 @@ import re
 import subprocess
 import sys
 import time
+
+TABLES = ["occurrence", "tree", "bloom1", "bloom2", "rep_t", "plcp", "text", "sa", "isa", "interval_slab_read", "interval_slab_write", "interval_out_write", "reads"]   # K1T_*
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,13 +45,20 @@ def main():
     ap.add_argument("--lib", default=None)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--commit", default=None, help="recorded in the output (the GPU box has no git)")
+    ap.add_argument("--trace-lib", default=None, help="the -DLH_K1_TRACE build to trace (default: tools/prof_rfa.sh's)")
+    ap.add_argument("--skip", action="append", default=[], help="comma-separated tables (names as in requests_by_table) the replay leaves out, on top of the earlier --skip")
     ap.add_argument("--kernel-stats", default=None, help="a tools/rocpd_stats.py CSV of the same build: k_smem_first's average duration goes into the output")
     a = ap.parse_args()
     if a.child:
         return child(a)
     out = {}
-    prof = os.path.join(ROOT, "lariat_amd", "_build", "liblariat_hip_prof.so")
-    for tag, lib, env in (("product", None, {}), ("trace", prof, {"LH_K1_TRACE": "1"})):
+    masks, m = [], 0
+    for grp in a.skip:
+        for name in grp.split(","):
+            m |= 1 << TABLES.index(name.strip())
+        masks.append(m)
+    prof = a.trace_lib or os.path.join(ROOT, "lariat_amd", "_build", "liblariat_hip_prof.so")
+    for tag, lib, env in (("product", None, {}), ("trace", prof, {"LH_K1_TRACE": "1", "LH_K1_REPLAY_SKIP": ",".join(str(v) for v in masks)})):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", "--genome-mb", str(a.genome_mb), "--barcodes", str(a.barcodes), "--steps", str(a.steps if lib is None else 2)]
         if lib:
             cmd += ["--lib", lib]
@@ -62,7 +73,12 @@ def main():
         else:
             m = [l for l in p.stderr.splitlines() if "K1TRACE" in l]
             tr = json.loads(m[-1].split("K1TRACE", 1)[1])
+            for w in tr.get("replay_without", []):
+                w["skip"] = [t for k, t in enumerate(TABLES) if (w["skip_mask"] >> k) & 1]
             out.update(tr)
+            ml = [l for l in p.stderr.splitlines() if "K1LENS" in l]
+            if ml:
+                out["list_lengths"] = json.loads(ml[-1].split("K1LENS", 1)[1])
             out["pass1_bracket_ms_while_tracing"] = round(tim[-1]["k_smem4"], 3)
     out["commit"] = a.commit
     if a.kernel_stats and os.path.exists(a.kernel_stats):
