@@ -95,16 +95,87 @@ def run_case(lib, oracle, seed):
         raise AssertionError("seed %d (%s): %s" % (seed, what, str(e)[:600]))
 
 
+def run_case_geometry(lib, oracle, seed, small=False):
+    """one random FRAGMENTED genome (helpers.fragmented_genome: a few long contigs and many short ones, some below min_seed_len, some overlapping
+    their neighbour, optional ALT mask) with geometry reads (helpers.geometry_reads: across junctions, off contig ends and l_pac, around contigs shorter
+    than the read, mates on unrelated contigs), random options, flags and context options; product against oracle (stage dumps and every result field).
+    small: genomes of at most ~300 kb and a few hundred pairs (the emulator build).  Returns helpers.geometry_coverage of the case; raises on a difference."""
+    rng = np.random.default_rng([seed, 0x6e0])
+    if small:
+        n_contigs = int(rng.choice([13, int(rng.integers(14, 80)), int(rng.integers(80, 400))]))
+        long_lens = tuple(int(rng.integers(5000, 40000)) for _ in range(int(rng.integers(1, 3))))
+        short_max = int(rng.choice([300, 1500, 4000])) if n_contigs > 100 else int(rng.choice([1500, 8000]))
+    else:
+        n_contigs = int(rng.choice([int(rng.integers(13, 200)), int(rng.integers(200, 1024)), int(rng.integers(1023, 2500))]))
+        long_lens = tuple(int(rng.integers(20000, 400000)) for _ in range(int(rng.integers(1, 4))))
+        short_max = int(rng.choice([2000, 8000, 30000])) if n_contigs < 200 else int(rng.choice([600, 2000, 6000]))
+    n_contigs = max(n_contigs, 12 + len(long_lens))
+    names, contigs, alt = helpers.fragmented_genome(seed, n_contigs, long_lens=long_lens, short_max=short_max, overlap_frac=float(rng.uniform(0.0, 0.4)),
+                                                    alt_frac=float(rng.choice([0.0, 0.1, 0.3])))
+    lens = [len(c) for c in contigs]
+    oidx = oracle.index_build_naive(names, contigs)
+    iopts = {}
+    if rng.random() < 0.3:
+        iopts["ktree_levels"] = int(rng.choice([-1, 3, 8, 11, 12]))
+    if rng.random() < 0.5:   # the device builder from the .pac (contigs shorter than min_seed_len included)
+        pac, l_pac, _, _ = lib.reference_pack(contigs)
+        offs = np.concatenate([[0], np.cumsum(lens)])
+        idx = lib.index_build_device(pac, l_pac, [(names[i], lens[i], int(offs[i])) for i in range(n_contigs)], build_chunk_log2=int(rng.choice([0, 12, 16])), **iopts)
+    else:
+        idx = lib.index_from_arrays(oidx.arrays(), **iopts)
+    if alt is not None:
+        idx.set_alt(alt); oidx.set_alt(alt)
+    l1, l2 = int(rng.integers(50, 241)), int(rng.integers(50, 241))
+    n_bc = int(rng.integers(1, 5 if small else 10))
+    pairs = [int(rng.integers(1, 60 if small else 200)) for _ in range(n_bc)]
+    if not small and rng.random() < 0.3:
+        pairs[0] = int(rng.integers(150, 400))   # a barcode of several hundred candidates (K8's wide grouping form)
+    w = rng.random(len(helpers.GEOMETRY_KINDS)) + 0.2
+    rs = helpers.geometry_reads(contigs, pairs, seed=seed + 11, len1=l1, len2=l2, ins_lo=int(rng.integers(150, 300)), ins_hi=int(rng.integers(300, 800)),
+                                sub_hi=float(rng.uniform(0.0, 0.06)), indel_frac=float(rng.choice([0.0, 0.05, 0.2])), n_frac=float(rng.choice([0.0, 0.05, 0.3])), weights=w)
+    rfa = (rng.random(n_bc) < 0.8).astype(np.uint8)
+    b = capi.Batch.from_arrays(rs.seq, rs.seq_off, rs.bc_pair_off, rs.name_seed, bc_do_rfa=rfa)
+    kw = {}
+    if rng.random() < 0.6:
+        kw["flags"] = int(rng.choice([capi.LH_F_EXT_SERIAL, capi.LH_F_EXT_WAVE, capi.LH_F_CHAIN_WAVE, capi.LH_F_P2_TASKS, capi.LH_F_RESCUE_FULL,
+                                      capi.LH_F_NO_SWEEP_FILTER, capi.LH_F_P2_TASKS | capi.LH_F_RESCUE_FULL, 0]))
+    if rng.random() < 0.3:
+        kw.update(b=int(rng.integers(2, 7)), o_del=int(rng.integers(3, 9)), o_ins=int(rng.integers(3, 9)), e_del=int(rng.integers(1, 3)), e_ins=int(rng.integers(1, 3)),
+                  w=int(rng.choice([20, 100])), zdrop=int(rng.choice([50, 100])), min_seed_len=int(rng.choice([15, 19, 25])))
+    copts = {"big_slots": int(rng.integers(1, 4))} if rng.random() < 0.1 else {}
+    what = "geometry: %d contigs (long %s, short up to %d), alt %s, reads %dx%d/%s, opts %s, index %s, context %s" % (
+        n_contigs, long_lens, short_max, None if alt is None else int(alt.sum()), l1, l2, pairs, kw, iopts, copts)
+    try:
+        ctx = idx.context(rs.n_pairs, **copts)
+        okw = {k: v for k, v in kw.items() if k != "flags"}
+        od = oidx.stage_dump(b, oracle.opts(**okw))
+        helpers.assert_same_dump(ctx.stage_dump(b, lib.opts(**kw)), od, helpers.DUMP_FRONT + helpers.DUMP_REGS)
+        want = oidx.align_barcodes(b, oracle.opts(**okw), threads=16)
+        helpers.assert_same_result(ctx.align_barcodes(b, lib.opts(**kw)), want, inference=True)
+    except Exception as e:
+        raise AssertionError("seed %d (%s): %s" % (seed, what, str(e)[:600]))
+    return helpers.geometry_coverage(lens, od, want, b)
+
+
+def add_coverage(total, cov):
+    """sums of geometry_coverage counts over cases (max_filtered: the largest)"""
+    for k, v in cov.items():
+        total[k] = max(total.get(k, 0), v) if k == "max_filtered" else total.get(k, 0) + v
+    return total
+
+
 if __name__ == "__main__":
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
+    geometry = "--geometry" in sys.argv   # the geometry leg (run_case_geometry) instead of run_case
+    args = [a for a in sys.argv[1:] if a != "--geometry"]
+    budget = float(args[0]) if len(args) > 0 else 120.0
+    seed0 = int(args[1]) if len(args) > 1 else 1000
     lib = capi.load_library()
     oracle = oracle_py.load()
     t_end = time.time() + budget
     it = 0
     while time.time() < t_end:
         try:
-            run_case(lib, oracle, seed0 + it)
+            (run_case_geometry if geometry else run_case)(lib, oracle, seed0 + it)
         except AssertionError as e:
             print("DIFF at " + str(e), flush=True)
             sys.exit(1)

@@ -367,3 +367,162 @@ def repeat_family_case(seed, n_barcodes, pairs=30):
     rs = synth.make_reads(wcontigs, wnames, n_barcodes=n_barcodes, pairs_per_barcode=pairs, seed=seed + 9, mol_min=2, mol_max=4, ins_mean=470, ins_sd=120, ins_max=900,
                           junk_frac=0.02)
     return names, contigs, rs
+
+
+def fragmented_genome(seed, n_contigs, long_lens=(150000,), short_max=8000, short_min=20, overlap_frac=0.15, alt_frac=0.0):
+    """a reference shaped like an analysis set's tail: `long_lens` long contigs plus n_contigs - len(long_lens) short ones whose lengths are
+    log-uniform in [short_min, short_max].  The short ones always include contigs shorter than min_seed_len (19), shorter than a read and
+    shorter than an insert; a fraction `overlap_frac` of the contigs start with a copy of the previous contig's last 30-400 bases (overlapping
+    scaffolds: a read across that junction has candidates on both sides).  Returns (names, contigs, alt) — alt a per-contig 0/1 mask when
+    alt_frac > 0 (never on the long contigs), else None."""
+    rng = np.random.default_rng(seed)
+    p = np.array([0.295, 0.205, 0.205, 0.295])
+    n_short = n_contigs - len(long_lens)
+    assert n_short >= 12
+    lens = np.exp(rng.uniform(np.log(short_min), np.log(short_max), size=n_short)).astype(np.int64)
+    lens[:12] = [12, 18, 19, 25, 40, 60, 90, 120, 140, 200, 300, 450]   # below min_seed_len, below a read, below an insert
+    rng.shuffle(lens)
+    lens = list(long_lens[:1]) + [int(x) for x in lens[:n_short // 2]] + list(long_lens[1:]) + [int(x) for x in lens[n_short // 2:]]
+    is_long = np.zeros(n_contigs, dtype=bool)
+    is_long[0] = True
+    is_long[1 + n_short // 2:1 + n_short // 2 + len(long_lens) - 1] = True
+    contigs = [rng.choice(4, size=int(n), p=p).astype(np.uint8) for n in lens]
+    for k in range(1, n_contigs):
+        if rng.random() < overlap_frac:
+            ov = min(int(rng.integers(30, 401)), len(contigs[k - 1]), len(contigs[k]))
+            contigs[k][:ov] = contigs[k - 1][len(contigs[k - 1]) - ov:]
+    names = ["frag%d" % k if not is_long[k] else "chr%d" % k for k in range(n_contigs)]
+    alt = None
+    if alt_frac > 0:
+        alt = ((rng.random(n_contigs) < alt_frac) & ~is_long).astype(np.uint8)
+    return names, contigs, alt
+
+
+GEOMETRY_KINDS = ("junction", "overhang", "inside_short", "split_mates", "ends", "plain", "rescue_edge")
+
+
+def geometry_reads(contigs, pairs_per_barcode, seed, len1=143, len2=150, ins_lo=250, ins_hi=600, sub_hi=0.02, indel_frac=0.05, n_frac=0.05,
+                   kinds=GEOMETRY_KINDS, weights=None):
+    """FR pairs drawn from the CONCATENATED reference without regard to contig boundaries, one barcode per entry of `pairs_per_barcode`.  Each
+    pair is one of `kinds`: across a junction between two contigs; hanging off a contig end (random bases beyond position 0 / l_pac, or past a
+    junction); around a contig shorter than the read; mates on two unrelated contigs; inside the first or last 600 bases of the concatenation;
+    anywhere; or mates that overlap almost entirely across a contig's start or end, one of them with a substitution every 10-16 bases (no seed:
+    only mem_matesw finds it, in a window that the contig end cuts).  Substitutions, some indels and some N's; names (hence name seeds) per pair.  Returns a synth.ReadSet whose `kind` lists the kinds."""
+    rng = np.random.default_rng(seed)
+    g = np.concatenate(contigs)
+    lpac = len(g)
+    clen = np.array([len(c) for c in contigs], dtype=np.int64)
+    coff = np.concatenate([[0], np.cumsum(clen)])
+    shorter = np.nonzero(clen < min(len1, len2))[0]
+    w = np.ones(len(kinds)) if weights is None else np.asarray(weights, dtype=float)
+    w = w / w.sum()
+
+    def seg(a, b):   # g[a:b] with random bases where it runs off either end of the concatenation
+        lo, hi = max(a, 0), min(b, lpac)
+        return np.concatenate([rng.integers(0, 4, size=max(0, lo - a)), g[lo:max(lo, hi)], rng.integers(0, 4, size=max(0, b - max(hi, lo)))]).astype(np.uint8)
+
+    n_pairs = int(np.sum(pairs_per_barcode))
+    reads, names, kind_of = [], [], []
+    for i in range(n_pairs):
+        kind = kinds[int(rng.choice(len(kinds), p=w))]
+        ins = int(rng.integers(max(ins_lo, len1, len2), ins_hi + 1))
+        if kind == "junction":     # the fragment or one of its reads across a junction
+            j = int(coff[int(rng.integers(1, len(contigs)))])
+            s = j - int(rng.integers(10, ins - 10))
+        elif kind == "overhang":   # a read past a contig end: off position 0, off l_pac, or across a junction by a few bases
+            r = rng.random()
+            if r < 0.3:
+                s = -int(rng.integers(5, len1 // 2))
+            elif r < 0.6:
+                s = lpac - ins + int(rng.integers(5, len2 // 2))
+            else:
+                j = int(coff[int(rng.integers(1, len(contigs)))])
+                s = j - len1 + int(rng.integers(3, 30)) if rng.random() < 0.5 else j + int(rng.integers(3, 30)) - ins
+        elif kind == "inside_short" and len(shorter):
+            k = int(rng.choice(shorter))
+            s = int(coff[k]) - int(rng.integers(0, len1 - clen[k] + 1)) if rng.random() < 0.5 else int(coff[k + 1]) - ins + int(rng.integers(0, len2 - clen[k] + 1))
+        elif kind == "rescue_edge":
+            k = int(rng.integers(1, len(contigs)))
+            ins = int(rng.integers(max(len1, len2), max(len1, len2) + 30))
+            d = int(rng.integers(5, 40))
+            s = int(coff[k]) - d if rng.random() < 0.5 else int(coff[k + 1]) + d - ins
+        elif kind == "ends":
+            s = int(rng.integers(0, 600 - 200)) if rng.random() < 0.5 else lpac - int(rng.integers(200, 600))
+            ins = min(ins, 600)
+        else:
+            s = int(rng.integers(0, lpac - ins))
+        frag = seg(s, s + ins)
+        r1, r2 = frag[:len1].copy(), _GEO_COMP[frag[ins - len2:][::-1]]
+        if kind == "split_mates":   # read 2 from another place entirely, either strand
+            t = int(rng.integers(0, lpac - len2))
+            r2 = g[t:t + len2].copy() if rng.random() < 0.5 else _GEO_COMP[g[t:t + len2][::-1]]
+        if kind == "rescue_edge":
+            r2 = r2.copy()
+            at = int(rng.integers(0, 10))
+            while at < len(r2):
+                r2[at] = (r2[at] + int(rng.integers(1, 4))) & 3
+                at += int(rng.integers(10, 17))
+        if rng.random() < 0.5:
+            r1, r2 = r2, r1
+        out = []
+        for r in (r1, r2):
+            m = rng.random(len(r)) < rng.uniform(0.0, sub_hi)
+            r[m] = (r[m] + rng.integers(1, 4, size=int(m.sum()))) & 3
+            if rng.random() < indel_frac:
+                at, ln = int(rng.integers(20, len(r) - 20)), int(rng.integers(1, 5))
+                r = np.concatenate([r[:at], r[at + ln:]]) if rng.random() < 0.5 else np.concatenate([r[:at], rng.integers(0, 4, size=ln).astype(np.uint8), r[at:]])
+            if rng.random() < n_frac:
+                r[rng.integers(0, len(r), size=int(rng.integers(1, 4)))] = 4
+            out.append(r.astype(np.uint8))
+        reads += out
+        names.append("geo:%d:%s:%d:%d" % (seed, kind, s, i))
+        kind_of.append(kind)
+    rs = synth.ReadSet()
+    lens = np.array([len(x) for x in reads], dtype=np.int64)
+    rs.seq_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    rs.seq = np.concatenate(reads)
+    rs.bc_pair_off = np.concatenate([[0], np.cumsum(pairs_per_barcode)]).astype(np.int32)
+    rs.names = names
+    rs.name_seed = synth._name_seeds(names)
+    rs.kind = kind_of
+    return rs
+
+
+_GEO_COMP = np.array([3, 2, 1, 0, 4], dtype=np.uint8)
+
+
+def geometry_coverage(contig_lens, od, ores, batch):
+    """how many of each contig-geometry edge a batch reached, read from the ORACLE's stage dump `od` and result `ores` (fwd||rev coordinates:
+    position x >= l_pac is forward position 2 l_pac - 1 - x)"""
+    clen = np.asarray(contig_lens, dtype=np.int64)
+    coff = np.concatenate([[0], np.cumsum(clen)])
+    lpac = int(coff[-1])
+
+    def fwd(b, e):   # [b, e) in fwd||rev -> forward [fb, fe)
+        rev = b >= lpac
+        return np.where(rev, 2 * lpac - e, b), np.where(rev, 2 * lpac - b, e)
+
+    sb, se = fwd(od.seed_rbeg, od.seed_rbeg + od.seed_len)
+    cross = (np.searchsorted(coff, sb, side="right") != np.searchsorted(coff, se - 1, side="right")) | ((od.seed_rbeg < lpac) & (od.seed_rbeg + od.seed_len > lpac))
+    rb, re = fwd(od.reg_rb, od.reg_re)
+    on_end = np.isin(rb, coff) | np.isin(re, coff)
+    c = ores.rid >= 0
+    rid = np.where(c, ores.rid, 0)
+    at_end = c & ((ores.pos == 0) | (ores.aend == clen[rid]))
+    rlen = np.diff(batch.seq_off)
+    read_of = np.repeat(np.arange(len(rlen)), np.diff(ores.cand_off))
+    ncand = np.diff(ores.cand_off[2 * batch.bc_pair_off.astype(np.int64)])
+    nfilt = np.add.reduceat(ores.in_filtered.astype(np.int64), ores.cand_off[2 * batch.bc_pair_off[:-1].astype(np.int64)]) if ores.n_cand else np.zeros(0)
+    return dict(bridging_seeds=int(cross.sum()), regions_on_contig_end=int(on_end.sum()), cand_pos0=int((c & (ores.pos == 0)).sum()),
+                cand_aend_at_contig_end=int((c & (ores.aend == clen[rid])).sum()), soft_clips_at_contig_end=int((at_end & (ores.soft_clipped > 0)).sum()),
+                cand_on_contig_shorter_than_read=int((c & (clen[rid] < rlen[read_of])).sum()), n_rescue=int(ores.counters["n_rescue"]),
+                barcodes_over_256=int((ncand > 256).sum()), barcodes_under_256=int((ncand <= 256).sum()), max_filtered=int(nfilt.max()) if len(nfilt) else 0)
+
+
+def assert_geometry_coverage(cov, **at_least):
+    """every count of geometry_coverage at least 1 (or the given minimum)"""
+    for k, v in cov.items():
+        if k == "max_filtered":
+            continue
+        need = at_least.get(k, 1)
+        assert v >= need, ("geometry coverage", k, v, need, cov)

@@ -4,7 +4,9 @@ windows through lh_diag_rescue_sw — the launches of the pipeline's rescue_dir 
   * random windows of every kind the probe saw (no hit, a diverged copy, a gapped copy, tandem copies that tie, a copy beside a shorter one): the certificate
     path and the whole-window path both give the oracle's (score, te, qe, tb, qb) wherever a region comes of the attempt, and agree that none does elsewhere;
   * crafted windows, one per term of the certificate: with the term in place the result is the oracle's; with that ONE term switched off (`weaken`) it is not —
-    every bound is there because a window exists that needs it.
+    every bound is there because a window exists that needs it;
+  * windows cut short by a contig end (mem_matesw clamps its window to the contig): 19 bases (min_seed_len) up to just under and just over the query's
+    length, holding the start or the end of the mate's copy where the contig ends, the whole copy, or nothing — both paths give the oracle's answer.
 
 The emulator runs them in `-m "not gpu"`, the device in `-m gpu`."""
 import ctypes as C
@@ -194,12 +196,58 @@ def _run_crafted(lib, oracle, seeds):
         assert k >= 0.85 * n, (name, k, n)
 
 
+def _cut_cases(rng, n):
+    """windows that a contig end has cut short (mem_matesw clamps its window to the contig of the midpoint): lengths from min_seed_len (19) up to just under and
+    just over the query's, holding the start or the end of a diverged copy of the mate cut where the contig ends, the whole copy, or nothing"""
+    Q, T = [], []
+    for case in range(n):
+        qlen = int(rng.integers(40, 151))
+        q = rng.integers(0, 4, size=qlen).astype(np.uint8)
+        tlen = int(rng.choice([MINSEED, MINSEED + 1, MINSEED + int(rng.integers(2, 12)), qlen // 2, qlen - 2, qlen - 1, qlen, qlen + 1, qlen + 2, qlen + 9]))
+        t = rng.integers(0, 4, size=tlen).astype(np.uint8)
+        c = q.copy()
+        m = rng.random(qlen) < [0.0, 0.02, 0.06][case % 3]
+        c[m] = (c[m] + rng.integers(1, 4, size=int(m.sum()))) & 3
+        kind = case % 4
+        if kind == 0:      # the window ends inside the copy: its first bases up to the contig end
+            k = min(tlen, qlen) - int(rng.integers(0, 4))
+            t[tlen - k:] = c[:k]
+        elif kind == 1:    # the window starts inside the copy: its last bases from the contig start
+            k = min(tlen, qlen) - int(rng.integers(0, 4))
+            t[:k] = c[qlen - k:]
+        elif kind == 2:    # as much of the copy as fits, somewhere
+            k = min(tlen, qlen)
+            a = int(rng.integers(0, qlen - k + 1)); at = int(rng.integers(0, tlen - k + 1))
+            t[at:at + k] = c[a:a + k]
+        Q.append(q); T.append(t)
+    return Q, T
+
+
+def _run_cut(lib, oracle, n, seed):
+    rng = np.random.default_rng(seed)
+    Q, T = _cut_cases(rng, n)
+    bad, got = _check(lib, oracle, Q, T)
+    assert bad == 0, bad
+    bad_full, got_full = _check(lib, oracle, Q, T, full=True)
+    assert bad_full == 0, bad_full
+    tl, ql = np.array([len(t) for t in T]), np.array([len(q) for q in Q])
+    hits = np.array([_oracle_sw(oracle, q, t)[0] >= MINSEED for q, t in zip(Q, T)])
+    # hits in windows at min_seed_len, shorter than the query, as long, longer; windows without one
+    assert (hits & (tl <= MINSEED + 1)).sum() > 0 and (hits & (tl < ql)).sum() > n // 8 and (hits & (tl == ql)).sum() > 0 and (hits & (tl > ql)).sum() > n // 16
+    assert (~hits).sum() > n // 16
+    return int(hits.sum())
+
+
 def test_emu_rescue_certificate_random_windows(emu, oracle):
     _run_random(emu, oracle, 240, 11)
 
 
 def test_emu_rescue_certificate_crafted_windows(emu, oracle):
     _run_crafted(emu, oracle, range(3, 33))
+
+
+def test_emu_rescue_certificate_cut_windows(emu, oracle):
+    _run_cut(emu, oracle, 400, 41)
 
 
 @pytest.mark.gpu
@@ -211,3 +259,9 @@ def test_rescue_certificate_random_windows(hip, oracle):
 @pytest.mark.gpu
 def test_rescue_certificate_crafted_windows(hip, oracle):
     _run_crafted(hip, oracle, range(3, 203))
+
+
+@pytest.mark.gpu
+def test_rescue_certificate_cut_windows(hip, oracle):
+    for seed in (42, 43):
+        _run_cut(hip, oracle, 2000, seed)
