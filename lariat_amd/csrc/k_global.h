@@ -187,8 +187,6 @@ __device__ __forceinline__ int grp_scan_max_i32(int v, int) {
 __device__ __forceinline__ int grp_shr1_i32(int v, int fill) { return LH_DPP(fill, v, 0x111, 0xF); }   // row_shr:1
 __device__ __forceinline__ int grp_shl1_i32(int v, int fill) { return LH_DPP(fill, v, 0x101, 0xF); }   // row_shl:1
 #endif
-__device__ __forceinline__ int grp_max_i32(int v) { for (int m = 8; m >= 1; m >>= 1) { int o = __shfl_xor(v, m); v = v > o ? v : o; } return v; }
-__device__ __forceinline__ int grp_sum_i32(int v) { for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m); return v; }
 
 // (r05) the same for groups of 32 lanes (two candidates per wave, bands up to 2 * 15 + 1 columns): a DPP row is 16 lanes, so the scan takes the row_bcast:15 step of the
 // wave-wide scan and the shifts are the wave's with the group's edge lanes filled

@@ -10,7 +10,7 @@
 //   k_resc_sw<true>              the reverse pass (KSW_XSTART) of the jobs that reached min_seed_len, bucketed by THEIR striping;
 //   k_resc_apply                 one wave per pair replays the loop in order with the jobs' results at hand: first test against the CURRENT
 //                                regions, insert, mem_sort_dedup_patch — an attempt that has become unnecessary drops its job's result, one that
-//                                has become necessary (a region that made it unnecessary was merged away) runs k_rescue.h's wave kernel in place.
+//                                has become necessary (a region that made it unnecessary was merged away) runs k_rescue.h's wave-wide ksw_align2 in place.
 //
 // The DP.  ksw_u8 is Farrar's striped kernel: lane L of 16 owns query columns [L * slen, (L + 1) * slen), F runs along a stripe inside the
 // main loop (F_seg: restarted at every stripe) and reaches later stripes only through the lazy-F loop, which repairs H but not E
@@ -994,7 +994,7 @@ __global__ void __launch_bounds__(64) k_resc_apply(DIndex ix, DOpts o, int n_pai
                 aln.score = J.score; aln.te = J.te; aln.qe = J.qe; aln.tb = J.tb; aln.qb = J.qb;
                 cells += (u64)(16 * ((l_ms + 15) / 16)) * (u64)J.tlen;
                 if (J.score >= o.min_seed_len * o.a) cells += (u64)(16 * ((J.qe + 1 + 15) / 16)) * (u64)J.rows2;
-            } else {   // no job: an attempt the enumeration saw as unnecessary (or left to this kernel): k_rescue.h's wave-wide kernel
+            } else {   // no job: an attempt the enumeration saw as unnecessary (or left to this kernel): k_rescue.h's wave-wide ksw_align2
                 RA_PROF(1)
                 const u64 cells_before = cells;
                 aln = wave_ksw_align2(ix, o, qm, l_ms - 1, -1, 1, l_ms, rb, 1, (int)(re - rb), o.min_seed_len * o.a, lane, &cells);

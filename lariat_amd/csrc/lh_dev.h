@@ -165,11 +165,6 @@ __device__ __forceinline__ i64 shfl_xor_i64(i64 v, int m) {
     lo = __shfl_xor(lo, m); hi = __shfl_xor(hi, m);
     return (i64)((u64)hi << 32 | lo);
 }
-__device__ __forceinline__ u64 shfl_up_u64(u64 v, int d) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl_up(lo, d); hi = __shfl_up(hi, d);
-    return (u64)hi << 32 | lo;
-}
 #ifdef LH_EMU
 __device__ __forceinline__ int wave_max_i32(int v) {
     for (int m = 32; m >= 1; m >>= 1) { int o = __shfl_xor(v, m); v = v > o ? v : o; }
@@ -272,15 +267,6 @@ __device__ __forceinline__ uint32_t dpp_xor2(uint32_t v) { return (uint32_t)__bu
 __device__ __forceinline__ uint32_t dpp_half_mirror(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true); }   // row_half_mirror
 __device__ __forceinline__ uint32_t dpp_ror8(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true); }   // row_ror:8
 #endif
-#ifdef LH_EMU
-template <int K> __device__ __forceinline__ uint32_t dpp_quad_bcast(uint32_t v) { return __shfl(v, (LANE() & ~3) | K); }
-#else
-template <int K> __device__ __forceinline__ uint32_t dpp_quad_bcast(uint32_t v) {   // quad_perm [K,K,K,K]
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, K | K << 2 | K << 4 | K << 6, 0xF, 0xF, true);
-}
-#endif
-template <int K> __device__ __forceinline__ u64 dpp_quad_bcast_u64(u64 v) { return (u64)dpp_quad_bcast<K>((uint32_t)(v >> 32)) << 32 | dpp_quad_bcast<K>((uint32_t)v); }
-__device__ __forceinline__ u64 dpp_ror8_u64(u64 v) { return (u64)dpp_ror8((uint32_t)(v >> 32)) << 32 | dpp_ror8((uint32_t)v); }
 
 // ------------------------------------------------------------------ k-mer membership filters
 #define LH_BLOOM_K 19   // = bwa's default min_seed_len: the filters are only consulted when opts.min_seed_len >= LH_BLOOM_K

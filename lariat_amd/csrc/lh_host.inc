@@ -8,6 +8,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <array>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -21,6 +23,7 @@
 #include "k_chain_cl.h"
 #include "k_rfa.h"   // pulls in k_seed/k_chain/k_extend/k_global/k_dedup/k_rescue/k_aln
 #include "k_rescue3.h"
+#include "lh_result_cols.h"
 
 #define LH_RFA_FIELDS DInf S; uint8_t* d_slab = nullptr; i64 slab_bytes = 0; int grid_rfa = 0; int32_t* d_bc_next = nullptr; \
     uint8_t* d_slab2 = nullptr; i64 slab2_bytes = 0; int grid_rfa2 = 0; uint8_t* d_slab_mid[2] = {nullptr, nullptr}; i64 slab_mid_bytes[2] = {0, 0}; int grid_rfa_mid[2] = {0, 0}; int grid_rfa_mid_max[2] = {0, 0}; int32_t* d_rfa_ovf_mid = nullptr; /* (r05) two tiers between the regular slabs and the few large ones */ int32_t* d_rfa_ovf = nullptr; int32_t* d_rfa_order = nullptr; int32_t *d_rfa_ovf2 = nullptr, *d_rfa_hp = nullptr, *d_rfa_hr = nullptr; double* d_bc_lmp = nullptr;

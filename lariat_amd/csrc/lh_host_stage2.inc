@@ -18,6 +18,40 @@ static int stage2_alloc(lh_context* c) {
     return LH_OK;
 }
 
+// a result column's array on the device
+static void* col_dev(lh_context* c, const ResultCol& k) {
+    switch (k.src) {
+    case FROM_CAND: return ptr_at(&c->R, k.dev_off);
+    case FROM_INF: return ptr_at(&c->S, k.dev_off);
+    case FROM_CIGAR_OFF: return c->d_cigar_off;
+    case FROM_MM_OFF: return c->d_mm_off;
+    case FROM_PACK_A: return c->d_pack_a;
+    case FROM_PACK_B: return c->d_pack_b;
+    default: return c->d_pack_c;
+    }
+}
+// n elements of a column set to its value in a result without inference
+static void fill_col(void* p, size_t n, const ResultCol& k) {
+    if (k.elt == 1) memset(p, (int)k.dflt, n);
+    else if (k.fp) std::fill_n((double*)p, n, k.dflt);
+    else if (k.elt == 8) std::fill_n((i64*)p, n, (i64)k.dflt);
+    else std::fill_n((int32_t*)p, n, (int32_t)k.dflt);
+}
+// the members of DCand / DInf that are result columns of one length class, with room for n elements
+static int alloc_result_cols(lh_context* c, ColLen len, size_t n) {
+    for (const ResultCol& k : LH_RESULT_COLS)
+        if (k.len == len && (k.src == FROM_CAND || k.src == FROM_INF)) {
+            uint8_t* p = nullptr;
+            DALLOC(p, n * k.elt);
+            set_ptr_at(k.src == FROM_CAND ? (void*)&c->R : (void*)&c->S, k.dev_off, p);
+        }
+    return LH_OK;
+}
+static void free_result_cols(lh_context* c, ColLen len) {
+    for (const ResultCol& k : LH_RESULT_COLS)
+        if (k.len == len && (k.src == FROM_CAND || k.src == FROM_INF)) hipFree(col_dev(c, k));
+}
+
 // everything sized by the number of candidates of a batch (cand_cap)
 static int alloc_cand_pools(lh_context* c) {
     DCand& R = c->R;
@@ -25,26 +59,18 @@ static int alloc_cand_pools(lh_context* c) {
     c->pack_cap = C * 8;
     DALLOC(c->d_cigar_off, C + 1); DALLOC(c->d_mm_off, C + 1); DALLOC(c->d_pack_a, c->pack_cap); DALLOC(c->d_pack_b, c->pack_cap); DALLOC(c->d_pack_c, c->pack_cap);
     DALLOC(c->d_tile_sum, C / LH_SCAN_TILE + 8);   // scans run over reads and over candidates
-    DALLOC(R.rid, C); DALLOC(R.pos, C); DALLOC(R.aend, C); DALLOC(R.rb, C); DALLOC(R.re, C); DALLOC(R.reversed, C); DALLOC(R.score, C); DALLOC(R.qb, C);
-    DALLOC(R.qe, C); DALLOC(R.nm, C); DALLOC(R.matches, C); DALLOC(R.mismatches, C); DALLOC(R.indels, C); DALLOC(R.soft_clipped, C);
-    DALLOC(R.soft_clipped_length, C); DALLOC(R.in_filtered, C); DALLOC(R.n_cigar, C); DALLOC(R.cigar, C * LH_MAX_CIGAR); DALLOC(R.n_mm, C);
-    DALLOC(R.mm_ref, C * LH_MAX_MM); DALLOC(R.mm_read, C * LH_MAX_MM); DALLOC(R.lap, C); DALLOC(R.read_len, C);
+    DALLOC(R.n_cigar, C); DALLOC(R.cigar, C * LH_MAX_CIGAR); DALLOC(R.n_mm, C); DALLOC(R.mm_ref, C * LH_MAX_MM); DALLOC(R.mm_read, C * LH_MAX_MM); DALLOC(R.read_len, C);
     R.mm_xcap = 1 << 22;   // loci beyond a candidate's slots: room for ~20,000 candidates that need it
     DALLOC(R.mm_xoff, C); DALLOC(R.mm_xref, R.mm_xcap); DALLOC(R.mm_xread, R.mm_xcap); DALLOC(R.mm_xctr, 1);
-    DInf& S = c->S;
-    DALLOC(S.active, C); DALLOC(S.is_proper, C); DALLOC(S.bwa_pick, C); DALLOC(S.active_molecule, C); DALLOC(S.duplicate, C); DALLOC(S.molecule_id, C);
-    DALLOC(S.mapq, C); DALLOC(S.mol_diff, C); DALLOC(S.mol_conf, C); DALLOC(S.sum_move, C); DALLOC(S.mate, C); DALLOC(S.cand_read, C);
-    return LH_OK;
+    DALLOC(c->S.cand_read, C);
+    return alloc_result_cols(c, PER_CAND, C);   // the per-candidate columns of the result (DCand's and DInf's)
 }
 static void free_cand_pools(lh_context* c) {
     DCand& R = c->R;
     hipFree(c->d_cigar_off); hipFree(c->d_mm_off); hipFree(c->d_pack_a); hipFree(c->d_pack_b); hipFree(c->d_pack_c); hipFree(c->d_tile_sum);
-    hipFree(R.rid); hipFree(R.pos); hipFree(R.aend); hipFree(R.rb); hipFree(R.re); hipFree(R.reversed); hipFree(R.score); hipFree(R.qb);
-    hipFree(R.qe); hipFree(R.nm); hipFree(R.matches); hipFree(R.mismatches); hipFree(R.indels); hipFree(R.soft_clipped); hipFree(R.soft_clipped_length);
-    hipFree(R.in_filtered); hipFree(R.n_cigar); hipFree(R.cigar); hipFree(R.n_mm); hipFree(R.mm_ref); hipFree(R.mm_read); hipFree(R.lap); hipFree(R.read_len); hipFree(R.mm_xoff); hipFree(R.mm_xref); hipFree(R.mm_xread); hipFree(R.mm_xctr);
-    DInf& S = c->S;
-    hipFree(S.active); hipFree(S.is_proper); hipFree(S.bwa_pick); hipFree(S.active_molecule); hipFree(S.duplicate); hipFree(S.molecule_id); hipFree(S.mapq);
-    hipFree(S.mol_diff); hipFree(S.mol_conf); hipFree(S.sum_move); hipFree(S.mate); hipFree(S.cand_read);
+    hipFree(R.n_cigar); hipFree(R.cigar); hipFree(R.n_mm); hipFree(R.mm_ref); hipFree(R.mm_read); hipFree(R.read_len); hipFree(R.mm_xoff); hipFree(R.mm_xref); hipFree(R.mm_xread); hipFree(R.mm_xctr);
+    hipFree(c->S.cand_read);
+    free_result_cols(c, PER_CAND);
 }
 
 static void stage2_free(lh_context* c) {
@@ -478,31 +504,16 @@ static int pipe_download_begin(lh_context* c) {
         c->pack_cap = (tc > tm ? tc : tm) + 1024;
         DALLOC(c->d_pack_a, c->pack_cap); DALLOC(c->d_pack_b, c->pack_cap); DALLOC(c->d_pack_c, c->pack_cap);
     }
-    // layout of the pinned block
+    // layout of the pinned block: the columns of LH_RESULT_COLS (lh_result_cols.h), then the counters' slots
     size_t total = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += (bytes + 63) & ~(size_t)63; return o; };
-    const size_t nC = (size_t)C, nN = (size_t)N;
-    struct Col { size_t off; const void* dev; size_t bytes; };
-    std::vector<Col> cols;
-    auto col = [&](const void* dev, size_t bytes) { size_t o = reserve(bytes); cols.push_back(Col{o, dev, bytes}); return o; };
-    DCand& R = c->R;
-    DInf& S = c->S;
-    const size_t o_cand_off = col(R.cand_off, (nN + 1) * 8), o_rid = col(R.rid, nC * 4), o_pos = col(R.pos, nC * 8), o_aend = col(R.aend, nC * 8), o_rb = col(R.rb, nC * 8),
-                 o_re = col(R.re, nC * 8), o_rev = col(R.reversed, nC), o_score = col(R.score, nC * 4), o_qb = col(R.qb, nC * 4), o_qe = col(R.qe, nC * 4), o_nm = col(R.nm, nC * 4),
-                 o_mat = col(R.matches, nC * 4), o_mis = col(R.mismatches, nC * 4), o_ind = col(R.indels, nC * 4), o_sc = col(R.soft_clipped, nC * 4),
-                 o_scl = col(R.soft_clipped_length, nC * 4), o_inf = col(R.in_filtered, nC), o_lap = col(R.lap, nC * 8),
-                 o_cigoff = col(c->d_cigar_off, (nC + 1) * 8), o_mmoff = col(c->d_mm_off, (nC + 1) * 8);
-    const size_t o_cig = reserve((size_t)tc * 4), o_mmr = reserve((size_t)tm * 4), o_mmq = reserve((size_t)tm * 4);
     const bool inf = c->ran_inference;
-    const size_t o_active = inf ? col(S.active, nC) : reserve(nC), o_proper = inf ? col(S.is_proper, nC) : reserve(nC), o_pick = inf ? col(S.bwa_pick, nC) : reserve(nC),
-                 o_amol = inf ? col(S.active_molecule, nC) : reserve(nC), o_dup = inf ? col(S.duplicate, nC) : reserve(nC),
-                 o_molid = inf ? col(S.molecule_id, nC * 4) : reserve(nC * 4), o_mapq = inf ? col(S.mapq, nC * 4) : reserve(nC * 4),
-                 o_mdiff = inf ? col(S.mol_diff, nC * 8) : reserve(nC * 8), o_mconf = inf ? col(S.mol_conf, nC * 8) : reserve(nC * 8),
-                 o_smove = inf ? col(S.sum_move, nC * 8) : reserve(nC * 8), o_mate = inf ? col(S.mate, nC * 8) : reserve(nC * 8),
-                 o_aidx = inf ? col(S.active_idx, nN * 8) : reserve(nN * 8), o_sbidx = inf ? col(S.second_best_idx, nN * 8) : reserve(nN * 8),
-                 o_sbsc = inf ? col(S.second_best_score, nN * 8) : reserve(nN * 8), o_as = inf ? col(S.as_score, nN * 8) : reserve(nN * 8),
-                 o_spidx = inf ? col(S.split_idx, nN * 8) : reserve(nN * 8), o_spmq = inf ? col(S.split_mapq, nN * 4) : reserve(nN * 4),
-                 o_spsb = inf ? col(S.split_second_best, nN * 8) : reserve(nN * 8), o_spsc = inf ? col(S.split_score, nN * 8) : reserve(nN * 8);
+    std::array<size_t, LH_N_COLS> cnt, off;   // per column: elements, place in the block
+    for (size_t i = 0; i < LH_N_COLS; ++i) {
+        cnt[i] = col_count(LH_RESULT_COLS[i], (size_t)N, (size_t)C, (size_t)tc, (size_t)tm);
+        off[i] = reserve(cnt[i] * LH_RESULT_COLS[i].elt);
+    }
+    DCand& R = c->R;
     const size_t o_ctr = reserve(sizeof(DCounters) * LH_CTR_SLOTS);
     total += 64;
     ResultArenaH* A = new ResultArenaH();
@@ -530,12 +541,9 @@ static int pipe_download_begin(lh_context* c) {
     }
     LH_FAIL(hipEventRecord(c->ev_pack, c->stream));
     LH_FAIL(hipStreamWaitEvent(c->dl_stream, c->ev_pack, 0));
-    for (const Col& k : cols)
-        if (k.bytes) LH_FAIL(hipMemcpyAsync(B + k.off, k.dev, k.bytes, hipMemcpyDeviceToHost, c->dl_stream));
-    if (C > 0) {
-        if (tc) LH_FAIL(hipMemcpyAsync(B + o_cig, c->d_pack_a, (size_t)tc * 4, hipMemcpyDeviceToHost, c->dl_stream));
-        if (tm) LH_FAIL(hipMemcpyAsync(B + o_mmq, c->d_pack_b, (size_t)tm * 4, hipMemcpyDeviceToHost, c->dl_stream));
-        if (tm) LH_FAIL(hipMemcpyAsync(B + o_mmr, c->d_pack_c, (size_t)tm * 4, hipMemcpyDeviceToHost, c->dl_stream));
+    for (size_t i = 0; i < LH_N_COLS; ++i) {   // every column straight to its place (an inference column only if the inference ran)
+        const ResultCol& k = LH_RESULT_COLS[i];
+        if (cnt[i] && (inf || k.src != FROM_INF)) LH_FAIL(hipMemcpyAsync(B + off[i], col_dev(c, k), cnt[i] * k.elt, hipMemcpyDeviceToHost, c->dl_stream));
     }
     LH_FAIL(hipEventRecord(c->ev_dl, c->dl_stream));
     LH_FAIL(hipStreamSynchronize(c->stream));   // (the counters and the pack kernels: short)
@@ -543,46 +551,20 @@ static int pipe_download_begin(lh_context* c) {
     c->dl_pending = true;
     c->dl_finish = [=](lh_result** out) -> int {
     if (hipEventSynchronize(c->ev_dl) != hipSuccess) { lh_result_free(&A->r); return set_err(LH_E_HIP, "the result's device-to-host copies failed"); }
-    if (!inf) {   // candidate generation only: the inference fields hold the Alignment defaults (lariat.go:1655-1689)
-        memset(B + o_active, 0, nC); memset(B + o_proper, 0, nC); memset(B + o_pick, 0, nC); memset(B + o_amol, 0, nC); memset(B + o_dup, 0, nC);
-        memset(B + o_mapq, 0, nC * 4); memset(B + o_mdiff, 0, nC * 8); memset(B + o_spmq, 0, nN * 4);
-        memset(B + o_sbsc, 0, nN * 8); memset(B + o_as, 0, nN * 8); memset(B + o_spsb, 0, nN * 8); memset(B + o_spsc, 0, nN * 8);
-        for (size_t i = 0; i < nC; ++i) { ((int32_t*)(B + o_molid))[i] = -1; ((double*)(B + o_mconf))[i] = 0.00075 * 0.025; ((double*)(B + o_smove))[i] = 1.0; ((i64*)(B + o_mate))[i] = -1; }
-        for (size_t i = 0; i < nN; ++i) { ((i64*)(B + o_aidx))[i] = -1; ((i64*)(B + o_sbidx))[i] = -1; ((i64*)(B + o_spidx))[i] = -1; }
-    }
-    DCounters ctr;
-    const DCounters* slots = (const DCounters*)(B + o_ctr);
-    memset(&ctr, 0, sizeof ctr);
-    for (int i = 0; i < LH_CTR_SLOTS; ++i) {
-        ctr.n_ext += slots[i].n_ext; ctr.n_lf += slots[i].n_lf; ctr.n_sa += slots[i].n_sa; ctr.win_bases += slots[i].win_bases; ctr.n_chain_ext += slots[i].n_chain_ext;
-        ctr.ext_cells += slots[i].ext_cells; ctr.glob_cells += slots[i].glob_cells; ctr.n_rescue += slots[i].n_rescue; ctr.rescue_cells += slots[i].rescue_cells;
-        for (int q = 0; q < 3; ++q) { ctr.n_ext_exec[q] += slots[i].n_ext_exec[q]; ctr.n_ktree[q] += slots[i].n_ktree[q]; }
-        ctr.n_bt += slots[i].n_bt; ctr.rescue_cells_exec += slots[i].rescue_cells_exec; ctr.n_glob_listed += slots[i].n_glob_listed; ctr.n_glob_exec += slots[i].n_glob_exec;
-    }
     lh_result& r = A->r;
     void* keep = r.arena_;
     memset(&r, 0, sizeof r);
     r.arena_ = keep;
     r.abi_version = LH_ABI_VERSION; r.n_reads = N; r.n_cand = C;
-    r.cand_off = (const i64*)(B + o_cand_off); r.rid = (const int32_t*)(B + o_rid); r.pos = (const i64*)(B + o_pos); r.aend = (const i64*)(B + o_aend);
-    r.rb = (const i64*)(B + o_rb); r.re = (const i64*)(B + o_re); r.reversed = (const uint8_t*)(B + o_rev); r.score = (const int32_t*)(B + o_score);
-    r.qb = (const int32_t*)(B + o_qb); r.qe = (const int32_t*)(B + o_qe); r.nm = (const int32_t*)(B + o_nm); r.matches = (const int32_t*)(B + o_mat);
-    r.mismatches = (const int32_t*)(B + o_mis); r.indels = (const int32_t*)(B + o_ind); r.soft_clipped = (const int32_t*)(B + o_sc);
-    r.soft_clipped_length = (const int32_t*)(B + o_scl); r.in_filtered = (const uint8_t*)(B + o_inf);
-    r.cigar_off = (const i64*)(B + o_cigoff); r.cigar = (const uint32_t*)(B + o_cig); r.mm_off = (const i64*)(B + o_mmoff);
-    r.mm_ref_loc = (const int32_t*)(B + o_mmr); r.mm_read_loc = (const int32_t*)(B + o_mmq);
-    r.log_alignment_probability = (const double*)(B + o_lap);
-    r.active = (const uint8_t*)(B + o_active); r.is_proper = (const uint8_t*)(B + o_proper); r.bwa_pick = (const uint8_t*)(B + o_pick);
-    r.active_molecule = (const uint8_t*)(B + o_amol); r.duplicate = (const uint8_t*)(B + o_dup); r.molecule_id = (const int32_t*)(B + o_molid);
-    r.mapq = (const int32_t*)(B + o_mapq); r.molecule_difference = (const double*)(B + o_mdiff); r.molecule_confidence = (const double*)(B + o_mconf);
-    r.sum_move_probability_change = (const double*)(B + o_smove); r.mate_idx = (const i64*)(B + o_mate);
-    r.active_idx = (const i64*)(B + o_aidx); r.second_best_idx = (const i64*)(B + o_sbidx); r.second_best_score = (const double*)(B + o_sbsc);
-    r.as_score = (const double*)(B + o_as); r.split_idx = (const i64*)(B + o_spidx); r.split_mapq = (const int32_t*)(B + o_spmq);
-    r.split_second_best = (const double*)(B + o_spsb); r.split_score = (const double*)(B + o_spsc);
-    r.n_ext = ctr.n_ext; r.n_lf = ctr.n_lf; r.n_sa = ctr.n_sa; r.win_bases = ctr.win_bases; r.n_chain_ext = ctr.n_chain_ext; r.ext_cells = ctr.ext_cells;
-    r.glob_cells = ctr.glob_cells; r.n_rescue = ctr.n_rescue; r.rescue_cells = ctr.rescue_cells;
-    r.n_ext_exec_p1 = ctr.n_ext_exec[0]; r.n_ext_exec_p2 = ctr.n_ext_exec[1]; r.n_ext_exec_p3 = ctr.n_ext_exec[2];
-    r.n_ktree_p1 = ctr.n_ktree[0]; r.n_ktree_p2 = ctr.n_ktree[1]; r.n_ktree_p3 = ctr.n_ktree[2]; r.n_calls_by_text = ctr.n_bt; r.rescue_cells_exec = ctr.rescue_cells_exec; r.n_glob_listed = ctr.n_glob_listed; r.n_glob_exec = ctr.n_glob_exec;
+    for (size_t i = 0; i < LH_N_COLS; ++i) {
+        const ResultCol& k = LH_RESULT_COLS[i];
+        if (!inf && k.src == FROM_INF) fill_col(B + off[i], cnt[i], k);   // candidate generation only: the inference fields hold the Alignment defaults (lariat.go:1655-1689)
+        set_ptr_at(&r, k.res_off, B + off[i]);
+    }
+    const uint64_t* slots = (const uint64_t*)(B + o_ctr);   // LH_CTR_SLOTS copies of DCounters: their sums are the result's counters
+    uint64_t* ctr = result_ctrs(&r);
+    for (size_t i = 0; i < LH_CTR_SLOTS; ++i)
+        for (size_t q = 0; q < LH_N_CTRS; ++q) ctr[q] += slots[i * LH_N_CTRS + q];
     *out = &A->r;
     return LH_OK;
     };
@@ -624,10 +606,8 @@ static int ext_alloc(lh_context* c) {
 }
 
 static int rfa_alloc(lh_context* c) {
-    i64 C = c->cand_cap, N = c->cap_reads;
-    DInf& S = c->S;
-    DALLOC(S.active_idx, N); DALLOC(S.second_best_idx, N); DALLOC(S.split_idx, N); DALLOC(S.second_best_score, N); DALLOC(S.as_score, N);
-    DALLOC(S.split_second_best, N); DALLOC(S.split_score, N); DALLOC(S.split_mapq, N);
+    i64 N = c->cap_reads;
+    { int rc = alloc_result_cols(c, PER_READ, N); if (rc) return rc; }   // the per-read columns of the result (DInf's)
     int want = c->co.rfa_grid;   // 16 single-wave blocks per CU = 4 waves per SIMD
     c->grid_rfa = c->cap_bc < want ? (int)c->cap_bc : want;
     c->slab_bytes = (i64)c->co.rfa_slab_kb << 10;
@@ -665,9 +645,7 @@ static int rfa_alloc(lh_context* c) {
 }
 
 static void rfa_free(lh_context* c) {
-    DInf& S = c->S;
-    hipFree(S.active_idx); hipFree(S.second_best_idx);
-    hipFree(S.split_idx); hipFree(S.second_best_score); hipFree(S.as_score); hipFree(S.split_second_best); hipFree(S.split_score); hipFree(S.split_mapq);
+    free_result_cols(c, PER_READ);
     hipFree(c->d_slab); hipFree(c->d_slab2); hipFree(c->d_slab_mid[0]); hipFree(c->d_slab_mid[1]); hipFree(c->d_rfa_ovf_mid); hipFree(c->d_rfa_ovf); hipFree(c->d_rfa_order); hipFree(c->d_bc_next); hipFree(c->d_rfa_ovf2); hipFree(c->d_rfa_hp); hipFree(c->d_rfa_hr); hipFree(c->d_bc_lmp);
 }
 

@@ -134,36 +134,27 @@ int lh_align_resident(lh_context* c, const lh_opts* opts) {
     return LH_OK;
 }
 
-// b's arrays behind a's in one block; candidate / CIGAR / mismatch indices of b shifted by a's totals
+// b's arrays behind a's in one block, column by column as LH_RESULT_COLS says (lh_result_cols.h): candidate / CIGAR / mismatch indices of b shifted by a's totals
 static int merge_results(lh_result* a, lh_result* b, lh_result** out) {
-    const size_t Na = (size_t)a->n_reads, Nb = (size_t)b->n_reads, Ca = (size_t)a->n_cand, Cb = (size_t)b->n_cand;
-    const size_t TCa = (size_t)a->cigar_off[Ca], TCb = (size_t)b->cigar_off[Cb], TMa = (size_t)a->mm_off[Ca], TMb = (size_t)b->mm_off[Cb];
-    const size_t N = Na + Nb, Cn = Ca + Cb;
+    const size_t Ca = (size_t)a->n_cand, Cb = (size_t)b->n_cand;
     size_t total = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += (bytes + 63) & ~(size_t)63; return o; };
-    struct Part { size_t off; const void* pa; size_t na; const void* pb; size_t nb; };
-    std::vector<Part> parts;
-    auto col = [&](const void* pa, const void* pb, size_t elt, size_t na, size_t nb) { size_t o = reserve((na + nb) * elt); parts.push_back(Part{o, pa, na * elt, pb, nb * elt}); return o; };
-    const size_t o_cand_off = reserve((N + 1) * 8), o_cigoff = reserve((Cn + 1) * 8), o_mmoff = reserve((Cn + 1) * 8);
-    const size_t o_mate = reserve(Cn * 8), o_aidx = reserve(N * 8), o_sbidx = reserve(N * 8), o_spidx = reserve(N * 8);
-#define MC(f, T) const size_t o_##f = col(a->f, b->f, sizeof(T), Ca, Cb)
-#define MR(f, T) const size_t o_##f = col(a->f, b->f, sizeof(T), Na, Nb)
-    MC(rid, int32_t); MC(pos, i64); MC(aend, i64); MC(rb, i64); MC(re, i64); MC(reversed, uint8_t); MC(score, int32_t); MC(qb, int32_t); MC(qe, int32_t);
-    MC(nm, int32_t); MC(matches, int32_t); MC(mismatches, int32_t); MC(indels, int32_t); MC(soft_clipped, int32_t); MC(soft_clipped_length, int32_t);
-    MC(in_filtered, uint8_t); MC(log_alignment_probability, double);
-    MC(active, uint8_t); MC(is_proper, uint8_t); MC(bwa_pick, uint8_t); MC(active_molecule, uint8_t); MC(duplicate, uint8_t); MC(molecule_id, int32_t);
-    MC(mapq, int32_t); MC(molecule_difference, double); MC(molecule_confidence, double); MC(sum_move_probability_change, double);
-    MR(second_best_score, double); MR(as_score, double); MR(split_mapq, int32_t); MR(split_second_best, double); MR(split_score, double);
-    const size_t o_cigar = col(a->cigar, b->cigar, 4, TCa, TCb), o_mmr = col(a->mm_ref_loc, b->mm_ref_loc, 4, TMa, TMb), o_mmq = col(a->mm_read_loc, b->mm_read_loc, 4, TMa, TMb);
+    std::array<size_t, LH_N_COLS> na, nb, off;   // per column: a's and b's elements, place in the block
+    for (size_t i = 0; i < LH_N_COLS; ++i) {
+        const ResultCol& k = LH_RESULT_COLS[i];
+        na[i] = col_count(k, (size_t)a->n_reads, Ca, (size_t)a->cigar_off[Ca], (size_t)a->mm_off[Ca]);
+        nb[i] = col_count(k, (size_t)b->n_reads, Cb, (size_t)b->cigar_off[Cb], (size_t)b->mm_off[Cb]);
+        off[i] = reserve((na[i] + nb[i] - (k.merge == MERGE_CONTINUE)) * k.elt);   // (b's entry 0 of an offset array is a's last)
+    }
     char* B = (char*)malloc(total + 64);
     if (!B) return set_err(LH_E_ARG, "out of memory merging the lanes' results");
-    {   // the plain columns, a few host threads
+    {   // a's part of every column and b's of the plain ones, a few host threads
         std::atomic<size_t> next{0};
         auto work = [&]() {
-            for (size_t k = next++; k < parts.size(); k = next++) {
-                const Part& p = parts[k];
-                if (p.na) memcpy(B + p.off, p.pa, p.na);
-                if (p.nb) memcpy(B + p.off + p.na, p.pb, p.nb);
+            for (size_t i = next++; i < LH_N_COLS; i = next++) {
+                const ResultCol& k = LH_RESULT_COLS[i];
+                if (na[i]) memcpy(B + off[i], ptr_at(a, k.res_off), na[i] * k.elt);
+                if (nb[i] && k.merge == MERGE_COPY) memcpy(B + off[i] + na[i] * k.elt, ptr_at(b, k.res_off), nb[i] * k.elt);
             }
         };
         std::vector<std::thread> th;
@@ -171,47 +162,26 @@ static int merge_results(lh_result* a, lh_result* b, lh_result** out) {
         work();
         for (auto& t : th) t.join();
     }
-    i64* cand_off = (i64*)(B + o_cand_off);
-    memcpy(cand_off, a->cand_off, (Na + 1) * 8);
-    for (size_t r = 1; r <= Nb; ++r) cand_off[Na + r] = b->cand_off[r] + (i64)Ca;
-    i64 *cigoff = (i64*)(B + o_cigoff), *mmoff = (i64*)(B + o_mmoff);
-    memcpy(cigoff, a->cigar_off, (Ca + 1) * 8); memcpy(mmoff, a->mm_off, (Ca + 1) * 8);
-    for (size_t k = 1; k <= Cb; ++k) { cigoff[Ca + k] = b->cigar_off[k] + (i64)TCa; mmoff[Ca + k] = b->mm_off[k] + (i64)TMa; }
-    i64* mate = (i64*)(B + o_mate);
-    memcpy(mate, a->mate_idx, Ca * 8);
-    for (size_t k = 0; k < Cb; ++k) mate[Ca + k] = b->mate_idx[k] < 0 ? b->mate_idx[k] : b->mate_idx[k] + (i64)Ca;
-    i64 *aidx = (i64*)(B + o_aidx), *sbidx = (i64*)(B + o_sbidx), *spidx = (i64*)(B + o_spidx);
-    memcpy(aidx, a->active_idx, Na * 8); memcpy(sbidx, a->second_best_idx, Na * 8); memcpy(spidx, a->split_idx, Na * 8);
-    for (size_t r = 0; r < Nb; ++r) {
-        aidx[Na + r] = b->active_idx[r] < 0 ? b->active_idx[r] : b->active_idx[r] + (i64)Ca;
-        sbidx[Na + r] = b->second_best_idx[r] < 0 ? b->second_best_idx[r] : b->second_best_idx[r] + (i64)Ca;
-        spidx[Na + r] = b->split_idx[r] < 0 ? b->split_idx[r] : b->split_idx[r] + (i64)Ca;
-    }
     ResultArenaH* A = new ResultArenaH();
     A->merged = B;
     lh_result& r = A->r;
     memset(&r, 0, sizeof r);
     r.arena_ = A;
-    r.abi_version = LH_ABI_VERSION; r.n_reads = (int32_t)N; r.n_cand = (int64_t)Cn;
-    r.cand_off = cand_off; r.cigar_off = cigoff; r.mm_off = mmoff; r.mate_idx = mate; r.active_idx = aidx; r.second_best_idx = sbidx; r.split_idx = spidx;
-#define SET(f, T) r.f = (const T*)(B + o_##f)
-    SET(rid, int32_t); SET(pos, i64); SET(aend, i64); SET(rb, i64); SET(re, i64); SET(reversed, uint8_t); SET(score, int32_t); SET(qb, int32_t); SET(qe, int32_t);
-    SET(nm, int32_t); SET(matches, int32_t); SET(mismatches, int32_t); SET(indels, int32_t); SET(soft_clipped, int32_t); SET(soft_clipped_length, int32_t);
-    SET(in_filtered, uint8_t); SET(log_alignment_probability, double);
-    SET(active, uint8_t); SET(is_proper, uint8_t); SET(bwa_pick, uint8_t); SET(active_molecule, uint8_t); SET(duplicate, uint8_t); SET(molecule_id, int32_t);
-    SET(mapq, int32_t); SET(molecule_difference, double); SET(molecule_confidence, double); SET(sum_move_probability_change, double);
-    SET(second_best_score, double); SET(as_score, double); SET(split_mapq, int32_t); SET(split_second_best, double); SET(split_score, double);
-    SET(cigar, uint32_t);
-    r.mm_ref_loc = (const int32_t*)(B + o_mmr); r.mm_read_loc = (const int32_t*)(B + o_mmq);
-#undef MC
-#undef MR
-#undef SET
-    r.n_ext = a->n_ext + b->n_ext; r.n_lf = a->n_lf + b->n_lf; r.n_sa = a->n_sa + b->n_sa; r.win_bases = a->win_bases + b->win_bases;
-    r.n_chain_ext = a->n_chain_ext + b->n_chain_ext; r.ext_cells = a->ext_cells + b->ext_cells; r.glob_cells = a->glob_cells + b->glob_cells;
-    r.n_rescue = a->n_rescue + b->n_rescue; r.rescue_cells = a->rescue_cells + b->rescue_cells;
-    r.n_ext_exec_p1 = a->n_ext_exec_p1 + b->n_ext_exec_p1; r.n_ext_exec_p2 = a->n_ext_exec_p2 + b->n_ext_exec_p2; r.n_ext_exec_p3 = a->n_ext_exec_p3 + b->n_ext_exec_p3;
-    r.n_ktree_p1 = a->n_ktree_p1 + b->n_ktree_p1; r.n_ktree_p2 = a->n_ktree_p2 + b->n_ktree_p2; r.n_ktree_p3 = a->n_ktree_p3 + b->n_ktree_p3;
-    r.n_calls_by_text = a->n_calls_by_text + b->n_calls_by_text; r.rescue_cells_exec = a->rescue_cells_exec + b->rescue_cells_exec; r.n_glob_listed = a->n_glob_listed + b->n_glob_listed; r.n_glob_exec = a->n_glob_exec + b->n_glob_exec;
+    r.abi_version = LH_ABI_VERSION; r.n_reads = a->n_reads + b->n_reads; r.n_cand = (int64_t)(Ca + Cb);
+    for (size_t i = 0; i < LH_N_COLS; ++i) {
+        const ResultCol& k = LH_RESULT_COLS[i];
+        set_ptr_at(&r, k.res_off, B + off[i]);
+        if (k.merge == MERGE_COPY) continue;
+        i64* dst = (i64*)(B + off[i]) + na[i];
+        const i64* src = (const i64*)ptr_at(b, k.res_off);
+        if (k.merge == MERGE_SHIFT)
+            for (size_t q = 0; q < nb[i]; ++q) dst[q] = src[q] < 0 ? src[q] : src[q] + (i64)Ca;
+        else {
+            const i64 last = dst[-1];   // a's last entry = b's entry 0
+            for (size_t q = 1; q < nb[i]; ++q) dst[q - 1] = src[q] + last;
+        }
+    }
+    for (size_t q = 0; q < LH_N_CTRS; ++q) result_ctrs(&r)[q] = result_ctrs(a)[q] + result_ctrs(b)[q];
     *out = &A->r;
     return LH_OK;
 }

@@ -264,10 +264,14 @@ def test_emu_two_lanes(emu, oracle):
     rfa = np.array([1, 1, 0, 1, 1], dtype=np.uint8)
     b = capi.Batch.from_arrays(rs.seq, rs.seq_off, rs.bc_pair_off, rs.name_seed, bc_do_rfa=rfa)
     ref = oidx.align_barcodes(b)
+    one_lane = idx.context(rs.n_pairs).align_barcodes(b)
+    assert len(one_lane.counters) == 19
     for lanes in (3, 2):
         ctx = idx.context(rs.n_pairs, lanes=lanes)
         res = ctx.align_barcodes(b)
         helpers.assert_same_result(res, ref, inference=True)
+        for k, v in one_lane.counters.items():   # every work counter is a sum over the reads: the lanes' parts add up to the one-lane run's
+            assert res.counters[k] == v, (lanes, k)
     for k in ("n_sa", "glob_cells", "n_rescue", "rescue_cells"):
         assert res.counters[k] == ref.counters[k], k
     # slots: two different batches resident, selected in turn

@@ -7,7 +7,7 @@ and off both ends of the concatenation, cover contigs shorter than themselves, o
 
   * mem_chain's skip of a seed that bridges two contigs or l_pac (k_chain.h, k_chain_cl.h, k_chain_lane.h);
   * mem_chain2aln's window clamped to [0, 2 l_pac), to one side of l_pac, to the seed's contig (k_extend.h; k_chain_lane.h dev_fetch_clamp);
-  * mem_matesw's window clamped to the contig of its midpoint, no attempt when too short (k_rescue.h, k_rescue2.h, k_rescue3.h): pairs whose mates overlap
+  * mem_matesw's window clamped to the contig of its midpoint, no attempt when too short (k_rescue2.h, k_rescue3.h): pairs whose mates overlap
     across a contig end, one of them without a seed;
   * mem_reg2aln's rejection of a region across l_pac (k_aln.h);
   * K8's grouping by contig (k_rfa.h): with 1,000 contigs the contig tables fit LDS (n_contigs + 2 <= LH_RFA_NCONT_LDS = 1024) — one barcode over
