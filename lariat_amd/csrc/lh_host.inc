@@ -15,6 +15,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
+#include <deque>
 #include <map>
 
 #include "../../include/lariat_hip.h"
@@ -24,21 +25,6 @@
 #include "k_rfa.h"   // pulls in k_seed/k_chain/k_extend/k_global/k_dedup/k_rescue/k_aln
 #include "k_rescue3.h"
 #include "lh_result_cols.h"
-
-#define LH_RFA_FIELDS DInf S; uint8_t* d_slab = nullptr; i64 slab_bytes = 0; int grid_rfa = 0; int32_t* d_bc_next = nullptr; \
-    uint8_t* d_slab2 = nullptr; i64 slab2_bytes = 0; int grid_rfa2 = 0; uint8_t* d_slab_mid[2] = {nullptr, nullptr}; i64 slab_mid_bytes[2] = {0, 0}; int grid_rfa_mid[2] = {0, 0}; int grid_rfa_mid_max[2] = {0, 0}; int32_t* d_rfa_ovf_mid = nullptr; /* (r05) two tiers between the regular slabs and the few large ones */ int32_t* d_rfa_ovf = nullptr; int32_t* d_rfa_order = nullptr; int32_t *d_rfa_ovf2 = nullptr, *d_rfa_hp = nullptr, *d_rfa_hr = nullptr; double* d_bc_lmp = nullptr;
-
-#define LH_STAGE2_FIELDS                                                                                         \
-    i64* d_reg_off = nullptr; DReg* d_regs = nullptr; DReg* d_regs_tmp = nullptr; int32_t* d_ia = nullptr;        \
-    int32_t* d_n_regs = nullptr; int32_t* d_best = nullptr; uint8_t* d_zpool = nullptr;                           \
-    uint8_t* d_reg_clean = nullptr;   /* K5's word per read: its list needs no look before K6's replay (k_dedup.h) */ \
-    int32_t* d_rnj = nullptr; i64* d_rjob_off = nullptr; RMeta* d_rmeta = nullptr; int32_t* d_rkeys = nullptr; RJob* d_rjobs = nullptr; int32_t *d_rorder = nullptr, *d_rorder2 = nullptr; i64 rjob_cap = 0;   /* K6's jobs (k_rescue2.h) */ \
-    i64 cand_cap = 0; int grid_aln = 0; DCand R; bool dump_stop_after_dedup = false; bool ran_inference = false;   \
-    i64* d_chain_rmax = nullptr; std::shared_ptr<PinPool> pin_pool = std::make_shared<PinPool>(); i64 *d_cigar_off = nullptr, *d_mm_off = nullptr; uint32_t *d_pack_a = nullptr, *d_pack_b = nullptr, *d_pack_c = nullptr; i64 pack_cap = 0; int32_t* d_rheavy = nullptr; int32_t *d_aln_r = nullptr, *d_aln_ci = nullptr, *d_aln_count = nullptr; int32_t *d_ext_defer = nullptr, *d_ext_heavy = nullptr, *d_ext_jlist = nullptr, *d_ext_jkey = nullptr, *d_ext_jorder = nullptr; ExtSt* d_ext_st = nullptr; DExtJobs* d_ext_jobs = nullptr; DExtJobs* d_ext_jobs2 = nullptr; int32_t* d_ext_long = nullptr; int32_t* d_ext_u = nullptr; \
-    LH_RFA_FIELDS
-#ifndef LH_RFA_FIELDS
-#define LH_RFA_FIELDS
-#endif
 
 static void lh_print_wd(const int32_t* d_wd) {   // (LH_DEBUG_SYNC builds of a run: the pipeline's watchdog slots after every launch)
     int32_t h[LH_WD_SLOTS];
@@ -54,6 +40,8 @@ static int set_err(int code, const std::string& m) { g_err = m; return code; }
         if (e_ != hipSuccess) { (void)hipGetLastError();   /* HIP's last-error slot is sticky: do not let this failure surface again in a later, unrelated call */ \
             return set_err(LH_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); }                      \
     } while (0)
+#include "lh_workspace.h"   // DevGroup, the counter blocks, the sectioned buffers
+
 
 // pinned host blocks that carry results (lh_result_download), recycled between batches
 struct PinBlock { char* p = nullptr; size_t cap = 0; };
@@ -90,11 +78,21 @@ struct lh_context {
     hipEvent_t ev_pack = nullptr, ev_dl = nullptr;
     bool dl_pending = false, dl_split = false; std::function<int(lh_result**)> dl_finish;
     int sel_slot = 0;
-    i64* h_peek = nullptr;   // page-locked, device-writable: small read-backs inside lh_align_resident (k_peek_i64); [4]: the previous batch's count of wave-chained reads
-    bool ext_hint_valid = false;
+    HostPeek* h_peek = nullptr;   // page-locked, device-writable: small read-backs inside lh_align_resident (lh_workspace.h)
+    bool ext_hint_valid = false;   // h_peek->prev_wave_reads holds a previous batch's count
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     i64 cap_pairs = 0, cap_reads = 0, cap_bases = 0, pool_cap = 0, regpool_cap = 0, cap_bc = 0;
-    int grid_smem4 = 0; PEnt* d_slab4 = nullptr; int32_t* d_next_read = nullptr;
+    // device memory by lifetime (lh_workspace.h).  mem: the whole context's; seed_mem follows a batch's seed total (pool_cap, regpool_cap: alloc_seed_pools), cand_mem its
+    // candidate total (cand_cap: alloc_cand_pools); regrown on their own: K1's big slab and list (big_cap), K6's job arrays (rjob_cap), the download's pack buffers
+    // (pack_cap), each K8 tier's slabs (grid_rfa_mid[k]).  A batch slot's arrays: DevBatch::mem
+    DevGroup mem, seed_mem, cand_mem, big_mem, rjob_mem, pack_mem, tier_mem[2];
+    void free_device() {   // everything this context owns on the device
+        for (DevGroup* g : {&mem, &seed_mem, &cand_mem, &big_mem, &rjob_mem, &pack_mem, &tier_mem[0], &tier_mem[1]}) g->release();
+        for (DevBatch& sl : slots) sl.mem.release();
+        for (void* q : free_later) hipFree(q);
+        free_later.clear();
+    }
+    int grid_smem4 = 0; PEnt* d_slab4 = nullptr; K1Counters* d_next_read = nullptr;
     // inputs
     uint32_t* d_seq4 = nullptr;   // the selected batch's reads as a 4-bit stream (k_pack_reads), two words of padding in front
     uint8_t* d_seq = nullptr; i64* d_seq_off = nullptr; u64* d_name_seed = nullptr; int32_t* d_bc_pair_off = nullptr; uint8_t* d_bc_do_rfa = nullptr;
@@ -102,31 +100,56 @@ struct lh_context {
     int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false; i64 n_bases = 0; const uint32_t* q4 = nullptr;
     int max_len = LH_MAXLEN;   // the selected batch's longest read (K1 stages its queries in that many bases' worth of LDS)
     // K1
-    DIntv* d_intv = nullptr; DIntv* d_big_slab = nullptr; int32_t *d_big_slot = nullptr, *d_big_list = nullptr, *d_big_count = nullptr; int big_cap = 0, big_base = 0;   // reads with more than LH_MAX_INTV intervals (k_smem4.h BIG)
-    K1Resume* d_k1_resume = nullptr; int32_t *d_k1_todo = nullptr, *d_p2_tasks = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read[6])
+    DIntv* d_intv = nullptr; DIntv* d_big_slab = nullptr; int32_t *d_big_slot = nullptr, *d_big_list = nullptr; K1BigCounts* d_big_count = nullptr; int big_cap = 0, big_base = 0;   // reads with more than LH_MAX_INTV intervals (k_smem4.h BIG)
+    K1Resume* d_k1_resume = nullptr; int32_t *d_k1_todo = nullptr, *d_p2_tasks = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read->n_todo)
     int32_t *d_n_intv = nullptr, *d_seed_cnt = nullptr, *d_l_rep = nullptr, *d_status = nullptr;
     // K2/K3
     i64* d_seed_off = nullptr; DSeed* d_seeds = nullptr; int32_t *d_s_rid = nullptr, *d_s_next = nullptr, *d_ord = nullptr, *d_srt = nullptr;
     DChainTmp* d_ct = nullptr; DChain* d_chains = nullptr; DSeed* d_cseeds = nullptr; int32_t* d_n_chains = nullptr;
     DCounters* d_ctr = nullptr; i64* d_tile_sum = nullptr;
     int32_t* d_wd = nullptr;   // this pipeline's watchdog slots (LH_WATCH through DOpts::wd): read back and cleared with its result
-    // later stages (allocated in lh_context_create, declared in lh_host_stage2.inc)
-    LH_STAGE2_FIELDS
+    // K4 (k_extend2.h); the region pools follow the seed pools
+    i64* d_reg_off = nullptr; DReg* d_regs = nullptr; int32_t* d_n_regs = nullptr; i64* d_chain_rmax = nullptr;
+    DReg* d_regs_tmp = nullptr;   // K5's and K6's region scratch; K7's lists (RegsTmpLists)
+    int32_t* d_ia = nullptr;
+    int32_t *d_ext_defer = nullptr, *d_ext_heavy = nullptr, *d_ext_jlist = nullptr, *d_ext_jkey = nullptr, *d_ext_jorder = nullptr; ExtSt* d_ext_st = nullptr;
+    DExtJobs* d_ext_jobs = nullptr; DExtJobs* d_ext_jobs2 = nullptr;   // the rounds' queue; the long queue's own (it runs beside them)
+    int32_t* d_ext_long = nullptr;   // the long queue's read lists (ExtLongLists)
+    int32_t* d_ext_u = nullptr;      // the long queue per chain slot (ExtUnits)
+    // K5, K6 (k_dedup.h, k_rescue2.h)
+    int32_t* d_best = nullptr;
+    uint8_t* d_reg_clean = nullptr;   // K5's word per read: its list needs no look before K6's replay (k_dedup.h)
+    int32_t* d_rnj = nullptr; i64* d_rjob_off = nullptr; RMeta* d_rmeta = nullptr; int32_t* d_rkeys = nullptr; int32_t* d_rheavy = nullptr;
+    RJob* d_rjobs = nullptr; int32_t *d_rorder = nullptr, *d_rorder2 = nullptr; i64 rjob_cap = 0;   // K6's jobs (k_rescue2.h): they follow the batch
+    // K7 (k_aln.h) and the result's candidate arrays
+    i64 cand_cap = 0; int grid_aln = 0; DCand R; uint8_t* d_zpool = nullptr;
+    int32_t *d_aln_r = nullptr, *d_aln_ci = nullptr; AlnCounts* d_aln_count = nullptr;   // candidate lists and their lengths (K3, K5 and K6 list reads there before)
+    i64 *d_cigar_off = nullptr, *d_mm_off = nullptr; uint32_t *d_pack_a = nullptr, *d_pack_b = nullptr, *d_pack_c = nullptr; i64 pack_cap = 0;   // the download's scans and packed arrays
+    std::shared_ptr<PinPool> pin_pool = std::make_shared<PinPool>();
+    bool dump_stop_after_dedup = false; bool ran_inference = false;
+    // K8 (k_rfa.h)
+    DInf S; uint8_t* d_slab = nullptr; i64 slab_bytes = 0; int grid_rfa = 0; RfaCounters* d_bc_next = nullptr;
+    uint8_t* d_slab2 = nullptr; i64 slab2_bytes = 0; int grid_rfa2 = 0;
+    uint8_t* d_slab_mid[2] = {nullptr, nullptr}; i64 slab_mid_bytes[2] = {0, 0}; int grid_rfa_mid[2] = {0, 0}; int grid_rfa_mid_max[2] = {0, 0};   // (r05) two tiers between the regular slabs and the few large ones
+    int32_t* d_rfa_ovf_mid = nullptr;   // the tiers' overflow lists (RfaOvfMid)
+    int32_t* d_rfa_order = nullptr;     // k_rfa_order's lists (RfaOrder)
+    int32_t *d_rfa_ovf = nullptr, *d_rfa_ovf2 = nullptr, *d_rfa_hp = nullptr, *d_rfa_hr = nullptr; double* d_bc_lmp = nullptr;
     // timings
     hipEvent_t ev[LH_NSTAGE + 1];
     const char* tnames[LH_NSTAGE];
     float tms[LH_NSTAGE];
     int n_t = 0;
     bool resident = false, ran = false;
-    // resident input batches: slot 0 lives in the capacity-sized buffers allocated at creation, further slots own exact-size copies;
-    // the d_seq ... d_cen_end pointers above always name the SELECTED slot
+    // resident input batches: slot 0 holds capacity-sized buffers allocated at creation, further slots own exact-size copies;
+    // the d_seq ... d_cen_end pointers above always name the SELECTED slot's
     struct DevBatch {
         uint8_t* seq = nullptr; i64* seq_off = nullptr; u64* name_seed = nullptr; int32_t* bc_pair_off = nullptr; uint8_t* bc_do_rfa = nullptr;
         i64 *cen_start = nullptr, *cen_end = nullptr;
+        DevGroup mem;   // the seven arrays above
         int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false, filled = false; i64 n_bases = 0; int max_len = LH_MAXLEN;
         i64 cap_bases = 0; int cap_reads = 0, cap_bc = 0;   // what the slot's own buffers hold (slots > 0)
     };
-    std::vector<DevBatch> slots; std::mutex slot_mu;   // slot_mu: slots' size and `filled`, sel_slot / resident, free_later
+    std::deque<DevBatch> slots; std::mutex slot_mu;   // slot_mu: slots' size and `filled`, sel_slot / resident, free_later.  (A deque: growing it does not move the slots another thread holds)
     std::vector<void*> free_later;   // device buffers a staging thread replaced: freed by the aligning thread
     lh_context_opts co;   // launch geometry (defaults filled in)
     uint32_t flags = 0;   // lh_opts.flags of the running call
@@ -190,40 +213,35 @@ static DOpts to_dopts(const lh_opts* o) {
 #include "lh_index.inc"
 
 // ------------------------------------------------------------------------------------------------ context
-template <class T> static int dalloc(T** p, size_t n) {
-    hipError_t e = hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
-    if (e != hipSuccess) { (void)hipGetLastError(); return set_err(LH_E_HIP, std::string("hipMalloc of ") + std::to_string((n ? n : 1) * sizeof(T)) + " bytes: " + hipGetErrorString(e)); }
-    return LH_OK;
-}
-#define DALLOC(p, n) do { int rc_ = dalloc(&(p), (size_t)(n)); if (rc_) return rc_; } while (0)
-
+#ifndef LH_POOL_FLOOR
+#define LH_POOL_FLOOR (1 << 16)   // the seed pools and the candidate pools start with room for this many entries at least
+#endif
 static int rfa_alloc(lh_context* c);
-static void rfa_free(lh_context* c);
 static int rfa_run(lh_context* c, const DOpts& o, int& t);
 static int stage2_alloc(lh_context* c);
-static void stage2_free(lh_context* c);
 static int stage2_run(lh_context* c, const DOpts& o, int& t);
 
 // pools whose size follows the number of seeds of a batch (pool_cap) or of regions (regpool_cap = seeds + rescue slots)
-static void free_seed_pools(lh_context* c) {
-    hipFree(c->d_seeds); hipFree(c->d_s_rid); hipFree(c->d_s_next); hipFree(c->d_ord); hipFree(c->d_srt); hipFree(c->d_ct); hipFree(c->d_chains); hipFree(c->d_cseeds);
-    c->d_seeds = nullptr; c->d_s_rid = nullptr; c->d_s_next = nullptr; c->d_ord = nullptr; c->d_srt = nullptr; c->d_ct = nullptr; c->d_chains = nullptr; c->d_cseeds = nullptr;
-    hipFree(c->d_regs); hipFree(c->d_regs_tmp); hipFree(c->d_ia); hipFree(c->d_aln_r); hipFree(c->d_aln_ci); hipFree(c->d_chain_rmax); hipFree(c->d_ext_u); c->d_ext_u = nullptr;
-    c->d_regs = nullptr; c->d_regs_tmp = nullptr; c->d_ia = nullptr; c->d_aln_r = nullptr; c->d_aln_ci = nullptr; c->d_chain_rmax = nullptr;
-}
-static int alloc_seed_pools(lh_context* c) {
-    DALLOC(c->d_seeds, c->pool_cap); DALLOC(c->d_s_rid, c->pool_cap); DALLOC(c->d_s_next, c->pool_cap);
-    DALLOC(c->d_ord, c->pool_cap); DALLOC(c->d_srt, c->pool_cap); DALLOC(c->d_ct, c->pool_cap); DALLOC(c->d_chains, c->pool_cap);
-    DALLOC(c->d_cseeds, c->pool_cap);
-    DALLOC(c->d_regs, c->regpool_cap); DALLOC(c->d_regs_tmp, c->regpool_cap); DALLOC(c->d_ia, c->regpool_cap + c->cap_reads + 8);
-    DALLOC(c->d_aln_r, c->regpool_cap); DALLOC(c->d_aln_ci, c->regpool_cap); DALLOC(c->d_chain_rmax, 2 * c->pool_cap);
-    DALLOC(c->d_ext_u, 10 * (size_t)c->pool_cap);   // K4's long queue, per chain slot: unit list, job list / keys / order, regions found, owner read (one int each), saved state (ExtSt)
+static int alloc_seed_pools(lh_context* c, i64 pool_cap) {
+    DevGroup& g = c->seed_mem;
+    g.release(); c->pool_cap = c->regpool_cap = 0;
+    const i64 regpool_cap = pool_cap + c->cap_reads * LH_RESCUE_SLOTS;
+    DALLOC(g, c->d_seeds, pool_cap); DALLOC(g, c->d_s_rid, pool_cap); DALLOC(g, c->d_s_next, pool_cap);
+    DALLOC(g, c->d_ord, pool_cap); DALLOC(g, c->d_srt, pool_cap); DALLOC(g, c->d_ct, pool_cap); DALLOC(g, c->d_chains, pool_cap);
+    DALLOC(g, c->d_cseeds, pool_cap);
+    DALLOC(g, c->d_regs, regpool_cap); DALLOC(g, c->d_regs_tmp, regpool_cap); DALLOC(g, c->d_ia, regpool_cap + c->cap_reads + 8);
+    DALLOC(g, c->d_aln_r, regpool_cap); DALLOC(g, c->d_aln_ci, regpool_cap); DALLOC(g, c->d_chain_rmax, 2 * pool_cap);
+    DALLOC(g, c->d_ext_u, ExtUnits::ints((size_t)pool_cap));
+    c->pool_cap = pool_cap; c->regpool_cap = regpool_cap;
     return LH_OK;
 }
-static int alloc_cand_pools(lh_context* c);
-static void free_cand_pools(lh_context* c);
+static int alloc_cand_pools(lh_context* c, i64 cand_cap);
+// the two pools' sizes in a new context; both grow on demand (run_front, stage2_run: a batch's totals are known before anything is written there)
+static i64 first_pool_cap(const lh_context* c) { return c->cap_reads * 16 > LH_POOL_FLOOR ? c->cap_reads * 16 : LH_POOL_FLOOR; }   // ~10 seeds per 150-base read at hg38 scale
+static i64 first_cand_cap(const lh_context* c) { return c->cap_reads * 3 > LH_POOL_FLOOR ? c->cap_reads * 3 : LH_POOL_FLOOR; }     // ~1.1 candidates/read on unique sequence
 
 static void pipe_free(lh_context* c);
+static void select_slot(lh_context* c, const lh_context::DevBatch& sl);
 struct CtxGuard { lh_context* c; ~CtxGuard() { if (c) pipe_free(c); } };
 
 static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* co, lh_context** out) {
@@ -243,8 +261,6 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
     c->cap_pairs = max_pairs; c->cap_reads = 2 * max_pairs;
     c->cap_bases = c->cap_reads * (i64)LH_MAXLEN;
     c->cap_bc = max_pairs;
-    c->pool_cap = c->cap_reads * 16 > (1 << 16) ? c->cap_reads * 16 : (1 << 16);   // ~10 seeds per 150-base read at hg38 scale; grown on demand (the total is known before K2 runs)
-    c->regpool_cap = c->pool_cap + c->cap_reads * LH_RESCUE_SLOTS;
     HIPCHK(hipStreamCreate(&c->stream));
     for (int i = 0; i < 3; ++i) { HIPCHK(hipStreamCreate(&c->aux[i])); HIPCHK(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming)); }
     HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -255,35 +271,34 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
         HIPCHK(hipStreamCreateWithPriority(&c->dl_stream, hipStreamNonBlocking, lo));
         HIPCHK(hipStreamCreateWithPriority(&c->up_stream, hipStreamNonBlocking, lo));
     }
-    HIPCHK(hipHostMalloc((void**)&c->h_peek, 64, hipHostMallocDefault));   // [0..3] K6 / K4 / totals, [4] the previous batch's wave-chained reads, [5] K8's overflow lists
+    HIPCHK(hipHostMalloc((void**)&c->h_peek, sizeof(HostPeek), hipHostMallocDefault));
     HIPCHK(hipEventCreateWithFlags(&c->ev_pack, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_dl, hipEventDisableTiming));
     i64 N = c->cap_reads;
-    DALLOC(c->d_seq4, c->cap_bases / 8 + 16); HIPCHK(hipMemset(c->d_seq4, 0x44, 16));
-    DALLOC(c->d_seq, c->cap_bases + 64); DALLOC(c->d_seq_off, N + 1); DALLOC(c->d_name_seed, max_pairs);
-    DALLOC(c->d_bc_pair_off, c->cap_bc + 1); DALLOC(c->d_bc_do_rfa, c->cap_bc);
-    DALLOC(c->d_cen_start, idx->names.size()); DALLOC(c->d_cen_end, idx->names.size());
+    DevGroup& g = c->mem;
+    DALLOC(g, c->d_seq4, c->cap_bases / 8 + 16); HIPCHK(hipMemset(c->d_seq4, 0x44, 16));
     {
-        lh_context::DevBatch s0;
-        s0.seq = c->d_seq; s0.seq_off = c->d_seq_off; s0.name_seed = c->d_name_seed; s0.bc_pair_off = c->d_bc_pair_off; s0.bc_do_rfa = c->d_bc_do_rfa;
-        s0.cen_start = c->d_cen_start; s0.cen_end = c->d_cen_end;
-        c->slots.reserve(4098);
-        c->slots.push_back(s0);
+        lh_context::DevBatch& s0 = c->slots.emplace_back();
+        DALLOC(s0.mem, s0.seq, c->cap_bases + 64); DALLOC(s0.mem, s0.seq_off, N + 1); DALLOC(s0.mem, s0.name_seed, max_pairs);
+        DALLOC(s0.mem, s0.bc_pair_off, c->cap_bc + 1); DALLOC(s0.mem, s0.bc_do_rfa, c->cap_bc);
+        DALLOC(s0.mem, s0.cen_start, idx->names.size()); DALLOC(s0.mem, s0.cen_end, idx->names.size());
+        select_slot(c, s0);
     }
-    DALLOC(c->d_intv, N * LH_MAX_INTV); DALLOC(c->d_n_intv, N);
+    DALLOC(g, c->d_intv, N * LH_MAX_INTV); DALLOC(g, c->d_n_intv, N);
     c->big_cap = c->co.big_slots > 0 ? c->co.big_slots : LH_MAX_INTV < 16 ? (int)N : (int)(N / 256 > 64 ? N / 256 : 64);   // (a test build with tiny regular slots sends most reads there)
-    DALLOC(c->d_k1_resume, N); DALLOC(c->d_k1_todo, N); DALLOC(c->d_p2_tasks, (size_t)LH_P2_SPLIT * N);
-    DALLOC(c->d_big_slab, (size_t)c->big_cap * 2 * LH_BIG_INTV); DALLOC(c->d_big_slot, N); DALLOC(c->d_big_list, c->big_cap); DALLOC(c->d_big_count, 2); DALLOC(c->d_seed_cnt, N); DALLOC(c->d_l_rep, N); DALLOC(c->d_status, N);
+    DALLOC(g, c->d_k1_resume, N); DALLOC(g, c->d_k1_todo, N); DALLOC(g, c->d_p2_tasks, (size_t)LH_P2_SPLIT * N);
+    DALLOC(c->big_mem, c->d_big_slab, (size_t)c->big_cap * 2 * LH_BIG_INTV); DALLOC(g, c->d_big_slot, N); DALLOC(c->big_mem, c->d_big_list, c->big_cap); DALLOC(g, c->d_big_count, 1);
+    DALLOC(g, c->d_seed_cnt, N); DALLOC(g, c->d_l_rep, N); DALLOC(g, c->d_status, N);
     {   // persistent-lane K1: 64 reads per wave in flight, as many waves as the device keeps resident (tunable for experiments)
         int want = c->co.smem_grid;
         i64 need = (c->cap_reads + 63) / 64;
         c->grid_smem4 = (int)(need < want ? need : want);
-        DALLOC(c->d_slab4, (size_t)c->grid_smem4 * 64 * 2 * (LH_MAXLEN + 2));
-        DALLOC(c->d_next_read, 8);   // [0..2] the passes' read counters, [3..5] the second chance's, [6] k_smem_first's list length, [7] pass 2's tasks
+        DALLOC(g, c->d_slab4, (size_t)c->grid_smem4 * 64 * 2 * (LH_MAXLEN + 2));
+        DALLOC(g, c->d_next_read, 1);
     }
-    DALLOC(c->d_seed_off, N + 1); DALLOC(c->d_n_chains, N);
-    { int rc = alloc_seed_pools(c); if (rc) return rc; }
-    DALLOC(c->d_ctr, LH_CTR_SLOTS);
-    DALLOC(c->d_wd, LH_WD_SLOTS);
+    DALLOC(g, c->d_seed_off, N + 1); DALLOC(g, c->d_n_chains, N);
+    { int rc = alloc_seed_pools(c, first_pool_cap(c)); if (rc) return rc; }
+    DALLOC(g, c->d_ctr, LH_CTR_SLOTS);
+    DALLOC(g, c->d_wd, LH_WD_SLOTS);
     HIPCHK(hipMemset(c->d_wd, 0, LH_WD_SLOTS * sizeof(int32_t)));
     { int rc = stage2_alloc(c); if (rc) return rc; }
     for (int i = 0; i <= LH_NSTAGE; ++i) HIPCHK(hipEventCreate(&c->ev[i]));
@@ -294,14 +309,7 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
 
 static void pipe_free(lh_context* c) {
     if (!c) return;
-    hipFree(c->d_seq4);
-    if (c->slots.empty()) { hipFree(c->d_seq); hipFree(c->d_seq_off); hipFree(c->d_name_seed); hipFree(c->d_bc_pair_off); hipFree(c->d_bc_do_rfa); hipFree(c->d_cen_start); hipFree(c->d_cen_end); }
-    for (void* q : c->free_later) hipFree(q);
-    for (auto& sl : c->slots) { hipFree(sl.seq); hipFree(sl.seq_off); hipFree(sl.name_seed); hipFree(sl.bc_pair_off); hipFree(sl.bc_do_rfa); hipFree(sl.cen_start); hipFree(sl.cen_end); }
-    hipFree(c->d_k1_resume); hipFree(c->d_k1_todo); hipFree(c->d_p2_tasks);
-    hipFree(c->d_intv); hipFree(c->d_big_slab); hipFree(c->d_big_slot); hipFree(c->d_big_list); hipFree(c->d_big_count); hipFree(c->d_n_intv); hipFree(c->d_seed_cnt); hipFree(c->d_l_rep); hipFree(c->d_status); hipFree(c->d_slab4); hipFree(c->d_next_read);
-    hipFree(c->d_seed_off); free_seed_pools(c); hipFree(c->d_n_chains); hipFree(c->d_ctr); hipFree(c->d_wd);
-    stage2_free(c);
+    c->free_device();
     for (int i = 0; i <= LH_NSTAGE; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
     for (int i = 0; i < 3; ++i) { if (c->aux[i]) hipStreamDestroy(c->aux[i]); if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]); }
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -344,10 +352,10 @@ static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool
         if (b->bc_pair_off[k + 1] < b->bc_pair_off[k]) return set_err(LH_E_ARG, "bc_pair_off must be non-decreasing (barcode " + std::to_string(k) + ")");
     size_t nc = c->idx->names.size();
     lh_context::DevBatch* slp;
-    {   // (the vector's storage was reserved at creation: growing it does not move the slots another thread holds)
+    {
         std::lock_guard<std::mutex> g(c->slot_mu);
         if (staged && c->resident && slot == c->sel_slot) return set_err(LH_E_ARG, "lh_batch_stage_slot: that slot is the selected one (stage into another, then lh_batch_select)");
-        if ((size_t)slot >= c->slots.size()) c->slots.resize((size_t)slot + 1);
+        while ((size_t)slot >= c->slots.size()) c->slots.emplace_back();
         slp = &c->slots[(size_t)slot];
         slp->filled = false;   // not selectable while its contents are being replaced (a failed copy leaves it so)
     }
@@ -356,13 +364,14 @@ static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool
         // buffers of its own (slot 0 uses the capacity-sized ones), kept while the next batch fits.  hipFree waits for the whole device: from
         // the staging thread it would sit behind the kernels the upload is meant to run beside, so the old buffers are handed to the thread
         // that aligns (pipe_align frees them before its first launch) or to lh_context_free
-        void* old[7] = {sl.seq, sl.seq_off, sl.name_seed, sl.bc_pair_off, sl.bc_do_rfa, sl.cen_start, sl.cen_end};
-        if (staged) { std::lock_guard<std::mutex> g(c->slot_mu); for (void* q : old) if (q) c->free_later.push_back(q); }
-        else for (void* q : old) hipFree(q);
-        sl = lh_context::DevBatch();
-        sl.cap_bases = nb + nb / 16; sl.cap_reads = n_reads; sl.cap_bc = b->n_barcodes;
-        DALLOC(sl.seq, (size_t)sl.cap_bases + 64); DALLOC(sl.seq_off, (size_t)n_reads + 1); DALLOC(sl.name_seed, (size_t)b->n_pairs);
-        DALLOC(sl.bc_pair_off, (size_t)b->n_barcodes + 1); DALLOC(sl.bc_do_rfa, (size_t)b->n_barcodes); DALLOC(sl.cen_start, nc); DALLOC(sl.cen_end, nc);
+        if (staged) { std::lock_guard<std::mutex> g(c->slot_mu); sl.mem.release_to(c->free_later); }
+        else sl.mem.release();
+        sl.cap_bases = 0; sl.cap_reads = 0; sl.cap_bc = 0;
+        const i64 cap_bases = nb + nb / 16;
+        DevGroup& g = sl.mem;
+        DALLOC(g, sl.seq, (size_t)cap_bases + 64); DALLOC(g, sl.seq_off, (size_t)n_reads + 1); DALLOC(g, sl.name_seed, (size_t)b->n_pairs);
+        DALLOC(g, sl.bc_pair_off, (size_t)b->n_barcodes + 1); DALLOC(g, sl.bc_do_rfa, (size_t)b->n_barcodes); DALLOC(g, sl.cen_start, nc); DALLOC(g, sl.cen_end, nc);
+        sl.cap_bases = cap_bases; sl.cap_reads = n_reads; sl.cap_bc = b->n_barcodes;
     }
     sl.n_pairs = b->n_pairs; sl.n_reads = n_reads; sl.n_bc = b->n_barcodes; sl.n_bases = nb; sl.max_len = (int)lmax;
     HIPCHK(hipMemcpyAsync(sl.seq, b->seq, (size_t)nb, hipMemcpyHostToDevice, us));
@@ -426,8 +435,18 @@ static ExtArgs ext_args(lh_context* c) {
     ExtArgs A;
     A.seq = c->d_seq; A.q4 = c->q4; A.seq_off = c->d_seq_off; A.seed_off = c->d_seed_off; A.chains = c->d_chains; A.cseeds = c->d_cseeds; A.n_chains = c->d_n_chains;
     A.sorder = c->d_srt; A.sdone = c->d_ord; A.chain_rmax = c->d_chain_rmax; A.reg_off = c->d_reg_off; A.regs = c->d_regs; A.n_regs = c->d_n_regs; A.est = c->d_ext_st;
-    A.nreg_u = c->d_ext_u + 4 * (size_t)c->pool_cap; A.u_read = c->d_ext_u + 5 * (size_t)c->pool_cap; A.est_u = (ExtSt*)(c->d_ext_u + 6 * (size_t)c->pool_cap); A.rflag = c->d_ext_long + 3 * (size_t)c->cap_reads;
+    const ExtUnits U(c->d_ext_u, (size_t)c->pool_cap);
+    A.nreg_u = U.nreg_u; A.u_read = U.u_read; A.est_u = U.est_u; A.rflag = ExtLongLists(c->d_ext_long, (size_t)c->cap_reads).rflag;
     return A;
+}
+
+#include "lh_host_trace.inc"   // the development aids' read-outs (LH_K1_TRACE, LH_RFA_PROF, LH_RA_HIST)
+
+// one pass of K1's state machine (k_smem4.h) on `grid` waves.  PASS names its read counter, the second chance's if BIG; QW: the instance by query staging; big: the
+// second chance's slab (BIG), else the list the pass works from (k_smem_first's reads, pass 2's tasks; none: every read)
+template <int PASS, bool BIG, int QW = 32> static void smem_pass(lh_context* c, const DIndex& ix4, const DOpts& o, int N, int grid, const K1Big& big) {
+    int32_t* const next = BIG ? &c->d_next_read->big_pass[PASS - 1] : &c->d_next_read->pass[PASS - 1];
+    LH_LAUNCH((k_smem_pass<PASS, BIG, QW>), grid, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, next, c->d_ctr, big);
 }
 
 // K1's second chance: the reads whose intervals outgrew their LH_MAX_INTV regular slots run the three passes again into slots of the big slab
@@ -436,15 +455,21 @@ static ExtArgs ext_args(lh_context* c) {
 static int k1_big_round(lh_context* c, const DOpts& o, const DIndex& ix4, int N, int base) {
     const int g4 = (N + 63) / 64 < c->grid_smem4 ? (N + 63) / 64 : c->grid_smem4;
     const int gb = g4 < 64 ? g4 : 64;   // a handful of reads, if any (the kernels read the count on the device: no host round trip)
-    HIPCHK(hipMemsetAsync(c->d_big_count, 0, 2 * sizeof(int32_t), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_next_read + 3, 0, 3 * sizeof(int32_t), c->stream));
-    K1Big big; big.list = c->d_big_list; big.count = c->d_big_count; big.slot = c->d_big_slot; big.slab = c->d_big_slab; big.resume = nullptr;
-    LH_LAUNCH(k_big_collect, (N + 255) / 256, 256, c->stream, N, c->d_status, c->d_n_intv, c->d_big_slot, c->d_big_list, c->d_big_count, base, c->big_cap - base);
-    LH_LAUNCH((k_smem_pass<1, true>), gb, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 3, c->d_ctr, big);
-    LH_LAUNCH((k_smem_pass<2, true>), gb, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 4, c->d_ctr, big);
-    if (o.max_mem_intv > 0)
-        LH_LAUNCH((k_smem_pass<3, true>), gb, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 5, c->d_ctr, big);
+    HIPCHK(hipMemsetAsync(c->d_big_count, 0, sizeof(K1BigCounts), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_next_read->big_pass, 0, sizeof c->d_next_read->big_pass, c->stream));
+    K1Big big; big.list = c->d_big_list; big.count = &c->d_big_count->listed; big.slot = c->d_big_slot; big.slab = c->d_big_slab; big.resume = nullptr;
+    LH_LAUNCH(k_big_collect, (N + 255) / 256, 256, c->stream, N, c->d_status, c->d_n_intv, c->d_big_slot, c->d_big_list, &c->d_big_count->listed, base, c->big_cap - base);
+    smem_pass<1, true>(c, ix4, o, N, gb, big);
+    smem_pass<2, true>(c, ix4, o, N, gb, big);
+    if (o.max_mem_intv > 0) smem_pass<3, true>(c, ix4, o, N, gb, big);
     LH_LAUNCH(k_smem_fin_big, gb, 64, c->stream, o, big, (const int32_t*)c->d_n_intv, c->d_seed_cnt, c->d_l_rep);
+    return LH_OK;
+}
+
+// the batch's seed total and the reads that asked for a slot of the big slab, on the host (h_peek->k1)
+static int peek_seed_total(lh_context* c, int N) {
+    LH_LAUNCH(k_peek_i64_i32, 1, 1, c->stream, (const i64*)(c->d_seed_off + N), (const int32_t*)&c->d_big_count->asked, &c->h_peek->k1.seeds);   // (not a copy-engine transfer: those may be busy with the previous result / the next batch)
+    HIPCHK(hipStreamSynchronize(c->stream));
     return LH_OK;
 }
 
@@ -463,125 +488,47 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
     if (c->flags & LH_F_NO_SWEEP_FILTER) ix4.bloom1 = ix4.bloom2 = nullptr;   // n_ext then counts every bwt_extend of the reference
     {   // K1: persistent lanes, one launch per pass of mem_collect_intv (k_smem4.h)
         const int g4 = (N + 63) / 64 < c->grid_smem4 ? (N + 63) / 64 : c->grid_smem4;
-        HIPCHK(hipMemsetAsync(c->d_next_read, 0, 8 * sizeof(int32_t), c->stream));   // one read counter per pass (+ the second chance's), [6]: reads k_smem_first left to pass 1
+        HIPCHK(hipMemsetAsync(c->d_next_read, 0, sizeof(K1Counters), c->stream));
         K1Big nobig; nobig.list = nullptr; nobig.count = nullptr; nobig.slot = nullptr; nobig.slab = nullptr; nobig.resume = nullptr;
-        K1Big first = nobig; first.list = c->d_k1_todo; first.count = c->d_next_read + 6; first.resume = c->d_k1_resume;
+        K1Big first = nobig; first.list = c->d_k1_todo; first.count = &c->d_next_read->n_todo; first.resume = c->d_k1_resume;
         const int g3 = (N + 63) / 64 < 2 * c->grid_smem4 ? (N + 63) / 64 : 2 * c->grid_smem4;   // pass 3 keeps no interval lists: the slab is not touched
         T_BEGIN("k_smem4");
         // every read's first bwt_smem1a call in lockstep, one thread per read; what it does not settle goes on in the state machine
-        LH_LAUNCH(k_smem_first, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_k1_resume, c->d_k1_todo, c->d_next_read + 6, c->d_ctr);
+        LH_LAUNCH(k_smem_first, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_k1_resume, c->d_k1_todo, &c->d_next_read->n_todo, c->d_ctr);
 #ifdef LH_K1_TRACE
-        u64* d_trace = nullptr; uint32_t* d_trace_n = nullptr; const uint32_t trace_cap = 4096;
-        unsigned long long* d_lens = nullptr;   // list lengths, passes 1 and 2 (k_smem4.h: K1_LEN)
-        const bool tracing = getenv("LH_K1_TRACE") != nullptr;
-        if (tracing) {
-            const size_t Tl = (size_t)g4 * 64;
-            DALLOC(d_trace, Tl * trace_cap); DALLOC(d_trace_n, Tl); DALLOC(d_lens, 2 * 3 * 64);
-            HIPCHK(hipMemsetAsync(d_trace_n, 0, Tl * 4, c->stream));
-            HIPCHK(hipMemsetAsync(d_lens, 0, 2 * 3 * 64 * 8, c->stream));
-            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_lens), &d_lens, sizeof d_lens, 0, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace), &d_trace, sizeof d_trace, 0, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace_cap), &trace_cap, sizeof trace_cap, 0, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace_n), &d_trace_n, sizeof d_trace_n, 0, hipMemcpyHostToDevice, c->stream));
-        }
+        K1Trace trace;
+        { int rc = k1_trace_begin(c, trace, g4); if (rc) return rc; }
 #endif
         // the instance whose query staging holds the batch's longest read: the LDS it leaves is the lists' ring (k_smem4.h: LH_K1_QW_SMALL)
         const bool qw_small = c->max_len <= 8 * LH_K1_QW_SMALL;
-        if (qw_small) LH_LAUNCH((k_smem_pass<1, false, LH_K1_QW_SMALL>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read, c->d_ctr, first);
-        else LH_LAUNCH((k_smem_pass<1, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read, c->d_ctr, first);
+        if (qw_small) smem_pass<1, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, first);
+        else smem_pass<1, false>(c, ix4, o, N, g4, first);
         T_END();
 #ifdef LH_K1_TRACE
-        if (tracing) {   // the request stream's own floor: the same sequences, the same geometry, nothing in between (tools/k1_trace.py reads the line)
-            u64* nul = nullptr;
-            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_trace), &nul, sizeof nul, 0, hipMemcpyHostToDevice, c->stream));
-            u64* d_sink = nullptr; unsigned long long* d_hist = nullptr;
-            DALLOC(d_sink, 1); DALLOC(d_hist, 2 * K1T_N + 2);
-            HIPCHK(hipMemsetAsync(d_hist, 0, (2 * K1T_N + 2) * 8, c->stream));
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            auto replay = [&](float& best, float& sum) -> int {
-                best = 1e30f; sum = 0;
-                for (int rep_ = 0; rep_ < 4; ++rep_) {
-                    HIPCHK(hipEventRecord(e0, c->stream));
-                    LH_LAUNCH(k_k1_replay, g4, 64, c->stream, (const u64*)d_trace, (const uint32_t*)d_trace_n, trace_cap, d_sink);
-                    HIPCHK(hipEventRecord(e1, c->stream));
-                    HIPCHK(hipEventSynchronize(e1));
-                    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-                    if (rep_) { sum += ms; best = ms < best ? ms : best; }   // (the first launch warms the trace's pages)
-                }
-                return LH_OK;
-            };
-            float best = 1e30f, sum = 0;
-            { int rc = replay(best, sum); if (rc) return rc; }
-            LH_LAUNCH(k_k1_trace_hist, 2048, 256, c->stream, (const u64*)d_trace, (const uint32_t*)d_trace_n, trace_cap, (uint32_t)(g4 * 64), d_hist);
-            unsigned long long h[2 * K1T_N + 2];
-            HIPCHK(hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            // LH_K1_REPLAY_SKIP = masks of tables (bit = K1T_*) separated by commas, each a superset of the one before: the replay again without them
-            std::string skip_js;
-            if (const char* sk = getenv("LH_K1_REPLAY_SKIP")) {
-                for (const char* q = sk; *q;) {
-                    char* end = nullptr;
-                    const unsigned long m = strtoul(q, &end, 0);
-                    if (end == q) break;
-                    LH_LAUNCH(k_k1_trace_skip, 2048, 256, c->stream, d_trace, d_trace_n, trace_cap, (uint32_t)(g4 * 64), (uint32_t)m);
-                    float b_ = 0, s_ = 0;
-                    { int rc = replay(b_, s_); if (rc) return rc; }
-                    skip_js += std::string(skip_js.empty() ? "" : ", ") + "{\"skip_mask\": " + std::to_string(m) + ", \"replay_ms_avg\": " + std::to_string(s_ / 3) + ", \"replay_ms_min\": " + std::to_string(b_) + "}";
-                    q = *end == ',' ? end + 1 : end;
-                }
-            }
-            static const char* const tn[K1T_N] = {"occurrence", "tree", "bloom1", "bloom2", "rep_t", "plcp", "text", "sa", "isa", "interval_slab_read", "interval_slab_write", "interval_out_write", "reads"};
-            std::string js = "{\"pairs\": " + std::to_string(N / 2) + ", \"lanes\": " + std::to_string((long long)g4 * 64) + ", \"replay_ms_avg\": " + std::to_string(sum / 3) + ", \"replay_ms_min\": " + std::to_string(best) +
-                             ", \"dropped_requests\": " + std::to_string(h[2 * K1T_N]) + ", \"requests_by_table\": {";
-            for (int i = 0; i < K1T_N; ++i) js += std::string(i ? ", " : "") + "\"" + tn[i] + "\": [" + std::to_string(h[2 * i]) + ", " + std::to_string(h[2 * i + 1]) + "]";
-            js += "}, \"replay_without\": [" + skip_js + "]}";
-            fprintf(stderr, "[lh] K1TRACE %s\n", js.c_str());
-            hipEventDestroy(e0); hipEventDestroy(e1);
-            hipFree(d_trace); hipFree(d_trace_n); hipFree(d_sink); hipFree(d_hist);
-        }
+        { int rc = k1_trace_replay(c, trace, N, g4); if (rc) return rc; }
 #endif
         T_BEGIN("k_smem4_p2");
         // the re-seeding calls as tasks: up to LH_P2_SPLIT lanes share a read's calls (k_smem4.h: P2TASK).  Worth its list when reads carry many such calls — reads on
         // repeat copies: pass 2 45 -> 31 ms on the repeat input, 29 -> 20 with 5 % of the pairs there, but 4.7 -> 5.4 ms on unique sequence — so, like K4's choice
         // of path and with the same sign (the wave-chained reads of the context's PREVIOUS batch), a choice of path and never of result
-        const bool p2_tasks = ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek[4] >= ext_long_min(N))) && N < (1 << 27);
+        const bool p2_tasks = ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek->prev_wave_reads >= ext_long_min(N))) && N < (1 << 27);
+        K1Big p2 = nobig;
         if (p2_tasks) {
-            K1Big p2 = nobig; p2.list = c->d_p2_tasks; p2.count = c->d_next_read + 7; p2.slot = c->d_k1_todo;   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
-            LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, c->d_next_read + 7, c->d_k1_todo);
-            if (qw_small) LH_LAUNCH((k_smem_pass<2, false, LH_K1_QW_SMALL>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, p2);
-            else LH_LAUNCH((k_smem_pass<2, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, p2);
-            LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
-        } else if (qw_small)
-        LH_LAUNCH((k_smem_pass<2, false, LH_K1_QW_SMALL>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, nobig);
-        else
-        LH_LAUNCH((k_smem_pass<2, false>), g4, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 1, c->d_ctr, nobig);
+            p2.list = c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo;   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
+            LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, &c->d_next_read->n_p2_tasks, c->d_k1_todo);
+        }
+        if (qw_small) smem_pass<2, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, p2);
+        else smem_pass<2, false>(c, ix4, o, N, g4, p2);
+        if (p2_tasks) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
         T_END();
 #ifdef LH_K1_TRACE
-        if (tracing) {   // the list lengths of passes 1 and 2 (tools/k1_trace.py reads the line)
-            unsigned long long* nul = nullptr;
-            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(lh_k1_lens), &nul, sizeof nul, 0, hipMemcpyHostToDevice, c->stream));
-            unsigned long long hl[2 * 3 * 64];
-            HIPCHK(hipMemcpyAsync(hl, d_lens, sizeof hl, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            static const char* const kn[3] = {"ncurr_at_push", "nprev_at_read", "stored_position_read"};
-            std::string js = "{";
-            for (int ps = 0; ps < 2; ++ps)
-                for (int k = 0; k < 3; ++k) {
-                    js += std::string(ps || k ? ", " : "") + "\"pass" + std::to_string(ps + 1) + "_" + kn[k] + "\": [";
-                    for (int v = 0; v < 64; ++v) js += std::string(v ? ", " : "") + std::to_string(hl[(ps * 3 + k) * 64 + v]);
-                    js += "]";
-                }
-            js += "}";
-            fprintf(stderr, "[lh] K1LENS %s\n", js.c_str());
-            hipFree(d_lens);
-        }
+        { int rc = k1_trace_lens(c, trace); if (rc) return rc; }
 #endif
         T_BEGIN("k_smem4_p3");
         if (o.max_mem_intv > 0 && q4)   // forward-only walks: one thread per read, in lockstep
             LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr);
         else if (o.max_mem_intv > 0)
-            LH_LAUNCH((k_smem_pass<3, false>), g3, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, c->d_next_read + 2, c->d_ctr, nobig);
+            smem_pass<3, false>(c, ix4, o, N, g3, nobig);
         T_END();
         T_BEGIN("k_smem_fin");
         // reads whose intervals outgrew their LH_MAX_INTV slots: the three passes again into the big slab (BWA's vectors grow: no read is refused)
@@ -593,44 +540,39 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
     { int rc = run_scan(c, N, c->d_seed_cnt, 0, 0, c->d_seed_off); if (rc) return rc; }
     T_END();
     {   // the seed pools (and the region pools derived from them) follow the batch: grow them before anything writes there
-        i64 total = 0;
-        LH_LAUNCH(k_peek_i64_i32, 1, 1, c->stream, (const i64*)(c->d_seed_off + N), (const int32_t*)(c->d_big_count + 1), c->h_peek);   // (not a copy-engine transfer: those may be busy with the previous result / the next batch)
-        HIPCHK(hipStreamSynchronize(c->stream));
-        while (c->h_peek[1] > (i64)(c->big_cap - c->big_base)) {
+        { int rc = peek_seed_total(c, N); if (rc) return rc; }
+        while (c->h_peek->k1.big_asked > (i64)(c->big_cap - c->big_base)) {
             // more reads asked for a slot of the big slab than it had (a batch of low-complexity reads): the slab grows by what is missing, the
             // reads left out run their second chance into the new slots, and the seed counts are scanned again.  (The loop ends: a round lists
             // every read that is still without a slot.)
-            const i64 asked = c->h_peek[1], old_cap = c->big_cap, new_cap = old_cap + asked + asked / 8 + 16;
+            const i64 asked = c->h_peek->k1.big_asked, old_cap = c->big_cap, new_cap = old_cap + asked + asked / 8 + 16;
             if (new_cap > (1 << 30)) return set_err(LH_E_CAPACITY, "too many reads with more than LH_MAX_INTV SMEM intervals for one batch: split the batch");
             DIntv* slab = nullptr; int32_t* list = nullptr;
-            DALLOC(slab, (size_t)new_cap * 2 * LH_BIG_INTV); DALLOC(list, (size_t)new_cap);
+            DevGroup grown;   // the new slab and list; once they are swapped in, the old ones
+            DALLOC(grown, slab, (size_t)new_cap * 2 * LH_BIG_INTV); DALLOC(grown, list, (size_t)new_cap);
             HIPCHK(hipMemcpyAsync(slab, c->d_big_slab, (size_t)old_cap * 2 * LH_BIG_INTV * sizeof(DIntv), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            hipFree(c->d_big_slab); hipFree(c->d_big_list);
-            c->d_big_slab = slab; c->d_big_list = list; c->big_base = (int)old_cap; c->big_cap = (int)new_cap;
+            HIPCHK(hipStreamSynchronize(c->stream));   // (the slab is copied before the old one is released)
+            std::swap(c->d_big_slab, slab); std::swap(c->d_big_list, list);   // (a buffer goes with the variable that holds it: DevGroup)
+            grown.release();
+            c->big_base = (int)old_cap; c->big_cap = (int)new_cap;
             { int rc = k1_big_round(c, o, ix4, N, c->big_base); if (rc) return rc; }
             { int rc = run_scan(c, N, c->d_seed_cnt, 0, 0, c->d_seed_off); if (rc) return rc; }
-            LH_LAUNCH(k_peek_i64_i32, 1, 1, c->stream, (const i64*)(c->d_seed_off + N), (const int32_t*)(c->d_big_count + 1), c->h_peek);
-            HIPCHK(hipStreamSynchronize(c->stream));
+            { int rc = peek_seed_total(c, N); if (rc) return rc; }
         }
         c->big_base = 0;
-        total = c->h_peek[0];
+        const i64 total = c->h_peek->k1.seeds;
         if (total > c->pool_cap) {
             // the pools follow the batch as far as HBM allows (a batch of low-complexity reads has up to max_occ seeds per interval: ~0.5 KB
             // of workspace per seed); what does not fit is a capacity error with its size, never a per-read refusal
-            free_seed_pools(c);
+            c->seed_mem.release(); c->pool_cap = c->regpool_cap = 0;
             size_t free_b = 0, total_b = 0;
             HIPCHK(hipMemGetInfo(&free_b, &total_b));
             const double per_seed = sizeof(DSeed) * 2 + 4 * 4 + sizeof(DChainTmp) + sizeof(DChain) + 16 + 2.0 * sizeof(DReg) + 12 + 40;
             const double need = ((double)total * 1.25 + (double)c->cap_reads * LH_RESCUE_SLOTS) * per_seed;
-            if (need > (double)free_b - 2e9) {
-                c->pool_cap = 0;
+            if (need > (double)free_b - 2e9)
                 return set_err(LH_E_CAPACITY, "the batch has " + std::to_string(total) + " seeds: their workspace (" + std::to_string((long long)(need / 1e9)) + " GB) does not fit the " +
                                                   std::to_string((long long)(free_b / 1000000000)) + " GB of HBM that are free: split the batch");
-            }
-            c->pool_cap = total + total / 4;
-            c->regpool_cap = c->pool_cap + c->cap_reads * LH_RESCUE_SLOTS;
-            int rc = alloc_seed_pools(c);
+            int rc = alloc_seed_pools(c, total + total / 4);
             if (rc) return rc;
         }
     }
@@ -656,7 +598,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         const int32_t* wlist = c->d_aln_r;
         const int32_t* wcount = c->d_ext_jobs->wave_range + 1;
         if (!(c->flags & LH_F_CHAIN_WAVE)) {
-            int32_t* const fb_count = c->d_aln_count + 3;
+            int32_t* const fb_count = &c->d_aln_count->full;   // (K7's counter: free until then)
             HIPCHK(hipMemsetAsync(fb_count, 0, sizeof(int32_t), c->stream));
             // (r06) the three instances take disjoint reads of the list (by seed count) and share nothing but the list of what they leave: side by side on three streams
             // (mixed input: 22.0 -> 20.5 ms; each instance alone already holds most of the waves its LDS use allows)
@@ -673,18 +615,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
 #undef LH_K3_CL
             wlist = c->d_aln_ci; wcount = fb_count;
 #ifdef LH_RFA_PROF
-            {
-                static const char* const names[8] = {"load + keys", "bitonic sort", "clusters", "cluster walks (lane per cluster)", "order + weights", "introsort", "greedy scan", "emit"};
-                unsigned long long h[16];
-                HIPCHK(hipStreamSynchronize(c->stream));
-                HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(lh_chain_prof), sizeof h));
-                unsigned long long tot = 0;
-                for (int i = 0; i < 8; ++i) tot += h[i];
-                fprintf(stderr, "[lh] k_chain_cl phases (%llu reads, %.1f k clocks per read):\n", h[15], h[15] ? (double)tot / 1e3 / (double)h[15] : 0.0);
-                for (int i = 0; i < 8; ++i) fprintf(stderr, "[lh]   %-36s %6.2f %%\n", names[i], tot ? 100.0 * (double)h[i] / (double)tot : 0.0);
-                memset(h, 0, sizeof h);
-                HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_chain_prof), h, sizeof h));
-            }
+            { int rc = prof_chain_cl(c); if (rc) return rc; }
 #endif
             if (lh_debug_sync()) {
                 int32_t nl = 0, nf = 0;
@@ -711,6 +642,9 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
         { std::lock_guard<std::mutex> g(c->slot_mu); fl.swap(c->free_later); }
         for (void* q : fl) hipFree(q);
     }
+    // a regrow that failed in an earlier call left the context without that group's buffers (capacity 0): start again with the sizes of a new context
+    if (!c->pool_cap) { int rc = alloc_seed_pools(c, first_pool_cap(c)); if (rc) return rc; }
+    if (!c->cand_cap) { int rc = alloc_cand_pools(c, first_cand_cap(c)); if (rc) return rc; }
     DOpts o = to_dopts(opts);
     o.wd = c->d_wd;
     c->flags = opts->flags;
@@ -777,7 +711,7 @@ int lh_stage_dump_resident(lh_context* c, const lh_opts* opts, lh_stage_dump** o
     std::vector<i64> seed_off;
     std::vector<DSeed> seeds;
     std::vector<DChain> chains;
-    K1Big big; big.list = c->d_big_list; big.count = c->d_big_count; big.slot = c->d_big_slot; big.slab = c->d_big_slab; big.resume = nullptr;
+    K1Big big; big.list = c->d_big_list; big.count = &c->d_big_count->listed; big.slot = c->d_big_slot; big.slab = c->d_big_slab; big.resume = nullptr;
     LH_LAUNCH(k_intv_rows, (N + 255) / 256, 256, c->stream, c->idx->d, N, c->d_intv, (const int32_t*)c->d_n_intv, big);   // K1 stores unique intervals by text position: the dump shows rows, like bwt_smem1a
     HIPCHK(hipStreamSynchronize(c->stream));
     D2H(n_intv, c->d_n_intv, N); D2H(intv, c->d_intv, (size_t)N * LH_MAX_INTV); D2H(seed_off, c->d_seed_off, N + 1); D2H(status, c->d_status, N);

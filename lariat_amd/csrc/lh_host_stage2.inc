@@ -4,15 +4,15 @@
 static int ext_alloc(lh_context* c);
 static int stage2_alloc(lh_context* c) {
     i64 N = c->cap_reads;
-    DALLOC(c->d_reg_off, N + 1);
-    DALLOC(c->d_n_regs, N); DALLOC(c->d_best, N);
-    DALLOC(c->d_reg_clean, N + 1); DALLOC(c->d_rnj, N / 2 + 1); DALLOC(c->d_rjob_off, N / 2 + 2); DALLOC(c->d_rmeta, 1); DALLOC(c->d_rheavy, N / 2 + 1); DALLOC(c->d_rkeys, 3 * LH_RC_KEYS);
-    c->cand_cap = N * 3 > (1 << 16) ? N * 3 : (1 << 16);   // ~1.1 candidates/read on unique sequence; grown on demand (stage2_run: the total is known before K7 runs)
+    DevGroup& g = c->mem;
+    DALLOC(g, c->d_reg_off, N + 1);
+    DALLOC(g, c->d_n_regs, N); DALLOC(g, c->d_best, N);
+    DALLOC(g, c->d_reg_clean, N + 1); DALLOC(g, c->d_rnj, N / 2 + 1); DALLOC(g, c->d_rjob_off, N / 2 + 2); DALLOC(g, c->d_rmeta, 1); DALLOC(g, c->d_rheavy, N / 2 + 1); DALLOC(g, c->d_rkeys, 3 * LH_RC_KEYS);
     c->grid_aln = c->co.aln_grid;   // 92 VGPRs: 5 waves per SIMD
-    DALLOC(c->d_zpool, (size_t)c->grid_aln * LH_ZSLAB);
-    DALLOC(c->d_aln_count, 4);   // [0]: candidates listed by k_aln_flat, [1]: what k_aln_flat2 lists for k_aln_grp<16> (k_aln_flat's list is [0]), [2]: candidates listed for k_aln_grp<32>, [3]: for k_aln
-    DALLOC(c->R.cand_off, N + 1);
-    { int rc = alloc_cand_pools(c); if (rc) return rc; }
+    DALLOC(g, c->d_zpool, (size_t)c->grid_aln * LH_ZSLAB);
+    DALLOC(g, c->d_aln_count, 1);
+    DALLOC(g, c->R.cand_off, N + 1);
+    { int rc = alloc_cand_pools(c, first_cand_cap(c)); if (rc) return rc; }
     { int rc = ext_alloc(c); if (rc) return rc; }
     { int rc = rfa_alloc(c); if (rc) return rc; }
     return LH_OK;
@@ -38,49 +38,38 @@ static void fill_col(void* p, size_t n, const ResultCol& k) {
     else std::fill_n((int32_t*)p, n, (int32_t)k.dflt);
 }
 // the members of DCand / DInf that are result columns of one length class, with room for n elements
-static int alloc_result_cols(lh_context* c, ColLen len, size_t n) {
+static int alloc_result_cols(lh_context* c, DevGroup& g, ColLen len, size_t n) {
     for (const ResultCol& k : LH_RESULT_COLS)
         if (k.len == len && (k.src == FROM_CAND || k.src == FROM_INF)) {
-            uint8_t* p = nullptr;
-            DALLOC(p, n * k.elt);
-            set_ptr_at(k.src == FROM_CAND ? (void*)&c->R : (void*)&c->S, k.dev_off, p);
+            uint8_t*& member = *(uint8_t**)((char*)(k.src == FROM_CAND ? (void*)&c->R : (void*)&c->S) + k.dev_off);
+            DALLOC(g, member, n * k.elt);
         }
     return LH_OK;
 }
-static void free_result_cols(lh_context* c, ColLen len) {
-    for (const ResultCol& k : LH_RESULT_COLS)
-        if (k.len == len && (k.src == FROM_CAND || k.src == FROM_INF)) hipFree(col_dev(c, k));
-}
 
-// everything sized by the number of candidates of a batch (cand_cap)
-static int alloc_cand_pools(lh_context* c) {
+// the download's staging buffers for the packed CIGAR / mismatch arrays: they follow the candidates, and grow on their own when a batch has more than 8 entries per candidate
+static int alloc_pack(lh_context* c, i64 pack_cap) {
+    DevGroup& g = c->pack_mem;
+    g.release(); c->pack_cap = 0;
+    DALLOC(g, c->d_pack_a, pack_cap); DALLOC(g, c->d_pack_b, pack_cap); DALLOC(g, c->d_pack_c, pack_cap);
+    c->pack_cap = pack_cap;
+    return LH_OK;
+}
+// everything sized by the number of candidates of a batch (cand_cap); DCand::cand_off is per read and stays
+static int alloc_cand_pools(lh_context* c, i64 C) {
     DCand& R = c->R;
-    i64 C = c->cand_cap;
-    c->pack_cap = C * 8;
-    DALLOC(c->d_cigar_off, C + 1); DALLOC(c->d_mm_off, C + 1); DALLOC(c->d_pack_a, c->pack_cap); DALLOC(c->d_pack_b, c->pack_cap); DALLOC(c->d_pack_c, c->pack_cap);
-    DALLOC(c->d_tile_sum, C / LH_SCAN_TILE + 8);   // scans run over reads and over candidates
-    DALLOC(R.n_cigar, C); DALLOC(R.cigar, C * LH_MAX_CIGAR); DALLOC(R.n_mm, C); DALLOC(R.mm_ref, C * LH_MAX_MM); DALLOC(R.mm_read, C * LH_MAX_MM); DALLOC(R.read_len, C);
+    DevGroup& g = c->cand_mem;
+    g.release(); c->cand_cap = 0;
+    DALLOC(g, c->d_cigar_off, C + 1); DALLOC(g, c->d_mm_off, C + 1);
+    { int rc = alloc_pack(c, C * 8); if (rc) { g.release(); return rc; } }
+    DALLOC(g, c->d_tile_sum, C / LH_SCAN_TILE + 8);   // scans run over reads and over candidates
+    DALLOC(g, R.n_cigar, C); DALLOC(g, R.cigar, C * LH_MAX_CIGAR); DALLOC(g, R.n_mm, C); DALLOC(g, R.mm_ref, C * LH_MAX_MM); DALLOC(g, R.mm_read, C * LH_MAX_MM); DALLOC(g, R.read_len, C);
     R.mm_xcap = 1 << 22;   // loci beyond a candidate's slots: room for ~20,000 candidates that need it
-    DALLOC(R.mm_xoff, C); DALLOC(R.mm_xref, R.mm_xcap); DALLOC(R.mm_xread, R.mm_xcap); DALLOC(R.mm_xctr, 1);
-    DALLOC(c->S.cand_read, C);
-    return alloc_result_cols(c, PER_CAND, C);   // the per-candidate columns of the result (DCand's and DInf's)
-}
-static void free_cand_pools(lh_context* c) {
-    DCand& R = c->R;
-    hipFree(c->d_cigar_off); hipFree(c->d_mm_off); hipFree(c->d_pack_a); hipFree(c->d_pack_b); hipFree(c->d_pack_c); hipFree(c->d_tile_sum);
-    hipFree(R.n_cigar); hipFree(R.cigar); hipFree(R.n_mm); hipFree(R.mm_ref); hipFree(R.mm_read); hipFree(R.read_len); hipFree(R.mm_xoff); hipFree(R.mm_xref); hipFree(R.mm_xread); hipFree(R.mm_xctr);
-    hipFree(c->S.cand_read);
-    free_result_cols(c, PER_CAND);
-}
-
-static void stage2_free(lh_context* c) {
-    hipFree(c->d_reg_off); hipFree(c->d_n_regs); hipFree(c->d_best);
-    hipFree(c->d_reg_clean); hipFree(c->d_rnj); hipFree(c->d_rjob_off); hipFree(c->d_rmeta); hipFree(c->d_rheavy); hipFree(c->d_rkeys); hipFree(c->d_rjobs); hipFree(c->d_rorder); hipFree(c->d_rorder2); hipFree(c->d_zpool); hipFree(c->d_aln_count);
-    hipFree(c->R.cand_off);
-    free_cand_pools(c);
-    hipFree(c->d_ext_defer); hipFree(c->d_ext_heavy);
-    hipFree(c->d_ext_st); hipFree(c->d_ext_jlist); hipFree(c->d_ext_jkey); hipFree(c->d_ext_jorder); hipFree(c->d_ext_jobs); hipFree(c->d_ext_jobs2); hipFree(c->d_ext_long);
-    rfa_free(c);
+    DALLOC(g, R.mm_xoff, C); DALLOC(g, R.mm_xref, R.mm_xcap); DALLOC(g, R.mm_xread, R.mm_xcap); DALLOC(g, R.mm_xctr, 1);
+    DALLOC(g, c->S.cand_read, C);
+    { int rc = alloc_result_cols(c, g, PER_CAND, C); if (rc) return rc; }   // the per-candidate columns of the result (DCand's and DInf's)
+    c->cand_cap = C;
+    return LH_OK;
 }
 
 // K6 (k_rescue2.h): per direction, the attempts that need a Smith-Waterman become jobs for the packed systolic kernel; a wave per pair then
@@ -93,17 +82,17 @@ template <int DIR> static int rescue_dir(lh_context* c, const DOpts& o, const DI
     LH_LAUNCH((k_resc_enum_w<DIR, false>), P < 8192 ? P : 8192, 64, c->stream, ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
               (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, (const i64*)nullptr, (RJob*)nullptr, (int32_t*)nullptr, c->d_rmeta, c->d_aln_r, (const int32_t*)c->d_rheavy);
     { int rc = run_scan(c, P, c->d_rnj, 0, 0, c->d_rjob_off); if (rc) return rc; }
-    LH_LAUNCH(k_resc_offsets, 1, 1, c->stream, c->d_rmeta, 0, c->h_peek, (const i64*)(c->d_rjob_off + P));
+    LH_LAUNCH(k_resc_offsets, 1, 1, c->stream, c->d_rmeta, 0, &c->h_peek->k6.total, (const i64*)(c->d_rjob_off + P));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const i64 total = c->h_peek[0], padded = c->h_peek[1], listed = c->h_peek[2], n_long = c->h_peek[3];
+    const i64 total = c->h_peek->k6.total, padded = c->h_peek->k6.padded, listed = c->h_peek->k6.listed, n_long = c->h_peek->k6.n_long;
     if (listed == 0) return LH_OK;
     if (total > 0) {
         const i64 cap2 = total + 8 * LH_RJ_NB;   // the reverse passes' order array: at most every job, each bucket padded to 8
         if (total > c->rjob_cap) {
-            hipFree(c->d_rjobs); hipFree(c->d_rorder); hipFree(c->d_rorder2);
-            c->d_rjobs = nullptr; c->d_rorder = nullptr; c->d_rorder2 = nullptr; c->rjob_cap = 0;
+            DevGroup& g = c->rjob_mem;
+            g.release(); c->rjob_cap = 0;
             const i64 cap = total + total / 4 + 1024;
-            DALLOC(c->d_rjobs, cap); DALLOC(c->d_rorder, cap + 8 * LH_RJ_NB); DALLOC(c->d_rorder2, cap + 8 * LH_RJ_NB);
+            DALLOC(g, c->d_rjobs, cap); DALLOC(g, c->d_rorder, cap + 8 * LH_RJ_NB); DALLOC(g, c->d_rorder2, cap + 8 * LH_RJ_NB);
             c->rjob_cap = cap;
         }
         HIPCHK(hipMemsetAsync(c->d_rorder, 0xff, (size_t)padded * 4, c->stream));
@@ -148,36 +137,10 @@ static int rescue_run(lh_context* c, const DOpts& o, const DIndex& ix) {
     { int rc = rescue_dir<0>(c, o, ix); if (rc) return rc; }   // read 1 from read 2's hits (gobwa.go:286-301)
     { int rc = rescue_dir<1>(c, o, ix); if (rc) return rc; }   // read 2 from read 1's hits, the rescued ones among them (gobwa.go:309-325)
 #ifdef LH_RFA_PROF
-    {
-        static const char* const names[8] = {"first test against the current list", "window + job result", "first look at the list (clean?)", "incremental dedup", "insert into the memory list", "mem_sort_dedup_patch as written", "reload + ties", "store"};
-        unsigned long long h[24];
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(lh_resc_prof), sizeof h));
-        unsigned long long tot = 0;
-        for (int i = 0; i < 8; ++i) tot += h[i];
-        fprintf(stderr, "[lh] k_resc_apply (both directions): %llu pairs replayed, %llu attempts; first look dirty %llu; calls decided incrementally %llu, declined (equal keys) %llu, as written %llu; lists left in memory: tie %llu, too long %llu; %.1f k clocks per pair\n",
-                h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[8] ? (double)tot / 1e3 / (double)h[8] : 0.0);
-        tot += h[16] + h[17];
-        for (int i = 0; i < 8; ++i) fprintf(stderr, "[lh]   %-36s %6.2f %%\n", names[i], tot ? 100.0 * (double)h[i] / (double)tot : 0.0);
-        fprintf(stderr, "[lh]   %-36s %6.2f %%\n[lh]   %-36s %6.2f %%   (%llu attempts without a job)\n", "loop head (anchors, job cursor)", tot ? 100.0 * (double)h[16] / (double)tot : 0.0,
-                "Smith-Waterman in place (no job)", tot ? 100.0 * (double)h[17] / (double)tot : 0.0, h[18]);
-        memset(h, 0, sizeof h);
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_resc_prof), h, sizeof h));
-    }
+    { int rc = prof_rescue(c); if (rc) return rc; }
 #endif
 #ifdef LH_RA_HIST
-    {
-        unsigned long long hh[66];
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpyFromSymbol(hh, HIP_SYMBOL(lh_resc_hist), sizeof hh));
-        for (int kind = 0; kind < 2; ++kind) {
-            fprintf(stderr, "[lh] k_resc_apply, time per pair, %s (longest %.3f ms):", kind ? "pairs with a call run as written" : "pairs decided incrementally", (double)hh[64 + kind] / 1e5);
-            for (int b = 0; b < 32; ++b) if (hh[kind * 32 + b]) fprintf(stderr, " <%.4g ms: %llu", (double)(2ull << b) / 1e5, hh[kind * 32 + b]);
-            fprintf(stderr, "\n");
-        }
-        memset(hh, 0, sizeof hh);
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_resc_hist), hh, sizeof hh));
-    }
+    { int rc = hist_rescue(c); if (rc) return rc; }
 #endif
     return LH_OK;
 }
@@ -199,51 +162,50 @@ static inline int ext_long_min(int N) { const int a = N / LH_EXT_LONG_DIV; retur
 static int ext_long_queue(lh_context* c, const DOpts& o, hipStream_t st) {
     const int N = c->n_reads;
     const DIndex& ix = c->idx->d;
-    const size_t cap = (size_t)c->cap_reads, pc = (size_t)c->pool_cap;
+    const ExtLongLists Q(c->d_ext_long, (size_t)c->cap_reads);
+    const ExtUnits U(c->d_ext_u, (size_t)c->pool_cap);
     DExtJobs* J = c->d_ext_jobs2;
-    int32_t *long_list = c->d_ext_long, *fb_list = long_list + cap, *defer = long_list + 2 * cap;   // (+ 3 cap: ExtArgs::rflag)
-    int32_t *ulist = c->d_ext_u, *jlist = ulist + pc, *jkey = ulist + 2 * pc, *jorder = ulist + 3 * pc;   // (+ 4 pc ..: ExtArgs::nreg_u, u_read, est_u)
     ExtArgs A = ext_args(c);
     const int gw = N < 16384 ? N : 16384;
     HIPCHK(hipMemsetAsync(J, 0, sizeof(DExtJobs), st));
     // J->wave_range[1]: the reads whose chains take the rounds; J->heavy_range: the ones k_extend prepares and extends (all of them when they are few);
     // J->defer_range: the ones k_ext_merge hands to k_extend; J->count[0]: the units; J->count[1], [2]: the queued jobs, in turn; J->count[3]: the calls for k_ext_wround
     LH_LAUNCH(k_ext_prep, gw, 64, st, ix, o, (const int32_t*)c->d_aln_r, (const int32_t*)c->d_ext_jobs->wave_range, ext_long_min(N), A, c->d_srt, c->d_chain_rmax,
-              c->d_ext_u + 5 * pc, long_list, J->wave_range + 1, fb_list, J->heavy_range + 1, ulist, J->count, c->d_ctr);
+              U.u_read, Q.long_list, J->wave_range + 1, Q.fb_list, J->heavy_range + 1, U.ulist, J->count, c->d_ctr);
     // (before the host looks at the queue: with few listed reads — the usual batch — this is all there is, and it should start at once)
-    LH_LAUNCH(k_extend, gw, 64, st, ix, o, N, (const int32_t*)fb_list, (const int32_t*)J->heavy_range, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
+    LH_LAUNCH(k_extend, gw, 64, st, ix, o, N, (const int32_t*)Q.fb_list, (const int32_t*)J->heavy_range, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
               c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, 1);
-    LH_LAUNCH(k_ext_round0, 2560, 64, st, ix, o, (const int32_t*)ulist, (const int32_t*)J->count, A, J->count + 1, jlist, jkey, c->d_ctr);
+    LH_LAUNCH(k_ext_round0, 2560, 64, st, ix, o, (const int32_t*)U.ulist, (const int32_t*)J->count, A, J->count + 1, U.jlist, U.jkey, c->d_ctr);
     int cur = 1;
     for (int rounds = 0;; rounds += LH_EXT_LONG_GROUP) {
-        LH_LAUNCH(k_peek_i32, 1, 1, st, (const int32_t*)(J->count + cur), c->h_peek);
+        LH_LAUNCH(k_peek_i32, 1, 1, st, (const int32_t*)(J->count + cur), &c->h_peek->one);
         HIPCHK(hipStreamSynchronize(st));
-        const i64 n_jobs = *c->h_peek;
+        const i64 n_jobs = c->h_peek->one;
         if (lh_debug_sync()) fprintf(stderr, "[lh] K4 long queue: %lld jobs queued after %d rounds\n", (long long)n_jobs, rounds);
         if (n_jobs < LH_EXT_LONG_TAIL || rounds >= 4096) {
-            if (n_jobs > 0) LH_LAUNCH(k_ext_flush, (int)((n_jobs + 255) / 256), 256, st, (const int32_t*)(J->count + cur), (const int32_t*)jlist, A);
+            if (n_jobs > 0) LH_LAUNCH(k_ext_flush, (int)((n_jobs + 255) / 256), 256, st, (const int32_t*)(J->count + cur), (const int32_t*)U.jlist, A);
             break;
         }
         const int gs = (int)((n_jobs + 1023) / 1024 < 256 ? (n_jobs + 1023) / 1024 : 256);
         for (int u = 0; u < LH_EXT_LONG_GROUP; ++u) {
             const int other = cur ^ 3;
-            LH_LAUNCH(k_extj_count, gs, 256, st, (const int32_t*)(J->count + cur), (const int32_t*)jkey, J);
+            LH_LAUNCH(k_extj_count, gs, 256, st, (const int32_t*)(J->count + cur), (const int32_t*)U.jkey, J);
             LH_LAUNCH(k_extj_offsets, 1, 256, st, J, cur, other);
-            LH_LAUNCH(k_extj_scatter, gs, 256, st, (const int32_t*)(J->count + cur), (const int32_t*)jkey, (const int32_t*)jlist, J, jorder);
-            LH_LAUNCH(k_ext_round<true>, 2560, 64, st, ix, o, (const int32_t*)(J->range + 2 * cur), J->next + cur, (const int32_t*)jorder, A, J->count + other, jlist, jkey,
-                      J->count + 3, ulist, c->d_ctr);   // (a unit's verdict 2: its call is made by a whole wave, next; the unit list is free after round 0)
-            LH_LAUNCH(k_ext_wround, gw, 64, st, ix, o, (const int32_t*)ulist, (const int32_t*)(J->count + 3), &J->wnext, A, J->count + other, jlist, jkey, c->d_ctr);
+            LH_LAUNCH(k_extj_scatter, gs, 256, st, (const int32_t*)(J->count + cur), (const int32_t*)U.jkey, (const int32_t*)U.jlist, J, U.jorder);
+            LH_LAUNCH(k_ext_round<true>, 2560, 64, st, ix, o, (const int32_t*)(J->range + 2 * cur), J->next + cur, (const int32_t*)U.jorder, A, J->count + other, U.jlist, U.jkey,
+                      J->count + 3, U.ulist, c->d_ctr);   // (a unit's verdict 2: its call is made by a whole wave, next; the unit list is free after round 0)
+            LH_LAUNCH(k_ext_wround, gw, 64, st, ix, o, (const int32_t*)U.ulist, (const int32_t*)(J->count + 3), &J->wnext, A, J->count + other, U.jlist, U.jkey, c->d_ctr);
             cur = other;
         }
     }
-    LH_LAUNCH(k_ext_merge, gw, 64, st, o, (const int32_t*)long_list, (const int32_t*)(J->wave_range + 1), A, c->d_regs_tmp, J->defer_range + 1, defer, J->kinds);
+    LH_LAUNCH(k_ext_merge, gw, 64, st, o, (const int32_t*)Q.long_list, (const int32_t*)(J->wave_range + 1), A, c->d_regs_tmp, J->defer_range + 1, Q.defer, J->kinds);
     if (lh_debug_sync()) {
         DExtJobs hj;
         if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(&hj, J, sizeof hj, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "[lh] K4 long queue: %d reads as %d chain units, %d reads left to k_extend before and %d after the rounds; (still queued: %d, more than %d regions: %d, a seed inside an earlier chain's region: %d); jobs: narrow %d + %d, live-interval %d + %d, short full-band %d + %d\n",
                     hj.wave_range[1], hj.count[0], hj.heavy_range[1], hj.defer_range[1], hj.kinds[0], LH_EXT_MERGE_CAP, hj.kinds[1], hj.kinds[2], hj.kinds[3], hj.kinds[6], hj.kinds[4], hj.kinds[7], hj.kinds[5], hj.kinds[8]);
     }
-    LH_LAUNCH(k_extend, gw, 64, st, ix, o, N, (const int32_t*)defer, (const int32_t*)J->defer_range, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
+    LH_LAUNCH(k_extend, gw, 64, st, ix, o, N, (const int32_t*)Q.defer, (const int32_t*)J->defer_range, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
               c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, 0);
     return LH_OK;
 }
@@ -289,7 +251,7 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
             // the reads the wave kernel chained, beside the rounds below.  Through the long queue or by the wave-per-read kernel: both give the same
             // regions, so the choice may rest on the PREVIOUS batch of this context — few such reads there (unique sequence) -> the wave-per-read
             // kernel at once; otherwise the long queue, after the rounds have been queued (the host looks at its length as it goes)
-            const i64 hint = c->ext_hint_valid ? c->h_peek[4] : -1;
+            const i64 hint = c->ext_hint_valid ? c->h_peek->prev_wave_reads : -1;
             long_q = !(hint >= 0 && hint < ext_long_min(N));
             if (!long_q) LH_EXT_WAVE(c->aux[0], c->d_ext_jobs->wave_range, c->d_aln_r, 1);
             LH_EXT_WAVE(c->aux[0], c->d_ext_jobs->heavy_range, c->d_ext_heavy, 0);   // a long side behind an indel or many mismatches (round 0's verdict)
@@ -306,7 +268,7 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
         }
         if (!serial) {
             if (long_q) { int rc = ext_long_queue(c, o, c->aux[0]); if (rc) return rc; }
-            LH_LAUNCH(k_peek_i32, 1, 1, c->aux[0], (const int32_t*)(c->d_ext_jobs->wave_range + 1), c->h_peek + 4);
+            LH_LAUNCH(k_peek_i32, 1, 1, c->aux[0], (const int32_t*)(c->d_ext_jobs->wave_range + 1), &c->h_peek->prev_wave_reads);
             c->ext_hint_valid = true;
             HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
             HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
@@ -335,10 +297,10 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
         }
     }
     T_BEGIN("k_dedup");
-    HIPCHK(hipMemsetAsync(c->d_aln_count, 0, sizeof(int32_t), c->stream));   // the list buffers are shared with K6 and K7, which run later
-    LH_LAUNCH(k_dedup_fast, (N + 255) / 256, 256, c->stream, ix, o, N, (const i64*)c->d_reg_off, c->d_regs, c->d_n_regs, c->d_best, c->d_aln_r, c->d_aln_count, c->d_reg_clean);
+    HIPCHK(hipMemsetAsync(&c->d_aln_count->flat, 0, sizeof(int32_t), c->stream));   // the list buffers are shared with K6 and K7, which run later
+    LH_LAUNCH(k_dedup_fast, (N + 255) / 256, 256, c->stream, ix, o, N, (const i64*)c->d_reg_off, c->d_regs, c->d_n_regs, c->d_best, c->d_aln_r, &c->d_aln_count->flat, c->d_reg_clean);
     LH_LAUNCH(k_dedup, N < 16384 ? N : 16384, 64, c->stream, ix, o, N, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_regs_tmp, c->d_ia, c->d_n_regs, c->d_best, c->d_ctr,
-              (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_count, c->d_reg_clean);
+              (const int32_t*)c->d_aln_r, (const int32_t*)&c->d_aln_count->flat, c->d_reg_clean);
     T_END();
     if (c->dump_stop_after_dedup) return LH_OK;
     T_BEGIN("k_rescue");
@@ -350,48 +312,40 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
     T_END();
     i64 total = 0;   // the batch's candidates (a read without a region has one: its placeholder)
     {   // the candidate arrays follow the batch: grow them before K7 writes there
-        LH_LAUNCH(k_peek_i64, 1, 1, c->stream, (const i64*)(c->R.cand_off + N), c->h_peek);
+        LH_LAUNCH(k_peek_i64, 1, 1, c->stream, (const i64*)(c->R.cand_off + N), &c->h_peek->one);
         HIPCHK(hipStreamSynchronize(c->stream));
-        total = *c->h_peek;
+        total = c->h_peek->one;
         if (total > c->cand_cap) {
             if (c->dl_pending) HIPCHK(hipEventSynchronize(c->ev_dl));   // (the arrays about to be replaced are being copied)
-            i64* keep = c->R.cand_off;
-            free_cand_pools(c);
-            c->cand_cap = total + total / 4;
-            c->R.cand_off = keep;
-            int rc = alloc_cand_pools(c);
+            int rc = alloc_cand_pools(c, total + total / 4);
             if (rc) return rc;
         }
     }
     T_BEGIN("k_aln_fast");
-    HIPCHK(hipMemsetAsync(c->d_aln_count, 0, 4 * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_aln_count, 0, sizeof(AlnCounts), c->stream));
     HIPCHK(hipMemsetAsync(c->R.mm_xctr, 0, sizeof(int32_t), c->stream));
     {   // (K5's and K6's per-read best scores are dead by now: d_best holds K7's; the read of every candidate slot goes where K8 will write the same numbers)
         const i64 n_cand = total < c->cand_cap ? total : c->cand_cap;
         LH_LAUNCH(k_aln_prep, (N + 255) / 256, 256, c->stream, o, N, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_status, c->d_best, c->S.cand_read);
         if (n_cand > 0)
             LH_LAUNCH(k_aln_flat, (int)((n_cand + 255) / 256), 256, c->stream, ix, o, n_cand, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, c->d_aln_r, c->d_aln_ci,
-                      c->d_aln_count, c->d_ctr, c->q4, (const int32_t*)c->d_best, (const int32_t*)c->S.cand_read);
+                      &c->d_aln_count->flat, c->d_ctr, c->q4, (const int32_t*)c->d_best, (const int32_t*)c->S.cand_read);
     }
     const int g7 = N < c->grid_aln ? N : c->grid_aln;
     T_END();
     T_BEGIN("k_aln");
-    int32_t* const wide_r = (int32_t*)c->d_regs_tmp;   // (K5's and K6's region scratch, regpool_cap x sizeof(DReg), is dead by now: the list of the candidates k_aln_grp hands on)
-    int32_t* const wide_ci = wide_r + c->regpool_cap;
-    static_assert(sizeof(DReg) >= 2 * sizeof(int32_t), "two lists in the region scratch");
-    // (r06) equal spans and five or six mismatches: a second, longer look without the DP (aln_deep_check) at what k_aln_flat listed; its list lies behind the other two
-    int32_t* const deep_r = wide_r + 2 * c->regpool_cap;
-    int32_t* const deep_ci = wide_r + 3 * c->regpool_cap;
-    static_assert(sizeof(DReg) >= 4 * sizeof(int32_t), "four lists in the region scratch");
+    const RegsTmpLists T7(c->d_regs_tmp, (size_t)c->regpool_cap);   // (K5's and K6's region scratch is dead by now: the lists of the candidates K7's kernels hand on)
+    AlnCounts* const n7 = c->d_aln_count;
+    // (r06) equal spans and five or six mismatches: a second, longer look without the DP (aln_deep_check) at what k_aln_flat listed
     LH_LAUNCH(k_aln_flat2, g7 < 2048 ? g7 : 2048, 256, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci,
-              (const int32_t*)c->d_aln_count, deep_r, deep_ci, c->d_aln_count + 1, c->d_ctr, c->q4, (const int32_t*)c->d_best);
-    LH_LAUNCH(k_aln_grp<16>, g7, 64, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)deep_r,
-              (const int32_t*)deep_ci, (const int32_t*)(c->d_aln_count + 1), wide_r, wide_ci, c->d_aln_count + 2);
+              (const int32_t*)&n7->flat, T7.deep_r, T7.deep_ci, &n7->grp16, c->d_ctr, c->q4, (const int32_t*)c->d_best);
+    LH_LAUNCH(k_aln_grp<16>, g7, 64, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)T7.deep_r,
+              (const int32_t*)T7.deep_ci, (const int32_t*)&n7->grp16, T7.wide_r, T7.wide_ci, &n7->grp32);
     // (r05) what four-per-wave in a band of 7 could not settle: two per wave in a band of 15; the first kernel's input list is free by now and takes what is still left for k_aln
-    LH_LAUNCH(k_aln_grp<32>, g7, 64, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)wide_r,
-              (const int32_t*)wide_ci, (const int32_t*)(c->d_aln_count + 2), c->d_aln_r, c->d_aln_ci, c->d_aln_count + 3);
+    LH_LAUNCH(k_aln_grp<32>, g7, 64, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)T7.wide_r,
+              (const int32_t*)T7.wide_ci, (const int32_t*)&n7->grp32, c->d_aln_r, c->d_aln_ci, &n7->full);
     LH_LAUNCH(k_aln, g7, 64, c->stream, ix, o, N, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_zpool, c->d_status, c->d_ctr,
-              (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci, (const int32_t*)(c->d_aln_count + 3));
+              (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci, (const int32_t*)&n7->full);
     T_END();
     if (o.run_inference) { int rc = rfa_run(c, o, t); if (rc) return rc; }
     return LH_OK;
@@ -459,11 +413,12 @@ static int pipe_download_begin(lh_context* c) {
     HIPCHK(hipSetDevice(c->idx->device));
     const int N = c->n_reads;
     // three small read-backs first: the OR of the status words, the candidate total, the packed CIGAR / mismatch totals
-    HIPCHK(hipMemsetAsync(c->d_aln_count, 0, sizeof(int32_t), c->stream));
-    if (N > 0) LH_LAUNCH(k_status_or, (N + 255) / 256, 256, c->stream, N, (const int32_t*)c->d_status, c->d_aln_count);
+    int32_t* const status_or = &c->d_aln_count->flat;   // (K7's counter: free by now)
+    HIPCHK(hipMemsetAsync(status_or, 0, sizeof(int32_t), c->stream));
+    if (N > 0) LH_LAUNCH(k_status_or, (N + 255) / 256, 256, c->stream, N, (const int32_t*)c->d_status, status_or);
     int32_t bad = 0;
     i64 C = 0;
-    HIPCHK(hipMemcpyAsync(&bad, c->d_aln_count, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&bad, status_or, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(&C, c->R.cand_off + N, sizeof C, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (bad & (LH_ST_INTV_OVERFLOW | LH_ST_CIGAR_OVERFLOW | LH_ST_MM_OVERFLOW | LH_ST_TOO_LONG)) {
@@ -499,10 +454,8 @@ static int pipe_download_begin(lh_context* c) {
     HIPCHK(hipMemcpyAsync(&tm, c->d_mm_off + C, sizeof tm, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (tc > c->pack_cap || tm > c->pack_cap) {   // more than 8 entries per candidate on average: grow the staging buffers
-        hipFree(c->d_pack_a); hipFree(c->d_pack_b); hipFree(c->d_pack_c);
-        c->d_pack_a = nullptr; c->d_pack_b = nullptr; c->d_pack_c = nullptr;
-        c->pack_cap = (tc > tm ? tc : tm) + 1024;
-        DALLOC(c->d_pack_a, c->pack_cap); DALLOC(c->d_pack_b, c->pack_cap); DALLOC(c->d_pack_c, c->pack_cap);
+        int rc = alloc_pack(c, (tc > tm ? tc : tm) + 1024);
+        if (rc) return rc;
     }
     // layout of the pinned block: the columns of LH_RESULT_COLS (lh_result_cols.h), then the counters' slots
     size_t total = 0;
@@ -599,25 +552,27 @@ void lh_result_free(lh_result* r) {
 
 // ------------------------------------------------------------------------------------------------ inference (K8)
 static int ext_alloc(lh_context* c) {
-    DALLOC(c->d_ext_defer, c->cap_reads); DALLOC(c->d_ext_heavy, c->cap_reads);
-    DALLOC(c->d_ext_st, c->cap_reads); DALLOC(c->d_ext_jlist, c->cap_reads); DALLOC(c->d_ext_jkey, c->cap_reads); DALLOC(c->d_ext_jorder, c->cap_reads); DALLOC(c->d_ext_jobs, 1);
-    DALLOC(c->d_ext_jobs2, 1); DALLOC(c->d_ext_long, 4 * (size_t)c->cap_reads);   // the long queue's own lists (it runs beside the rounds of the other reads)
+    DevGroup& g = c->mem;
+    DALLOC(g, c->d_ext_defer, c->cap_reads); DALLOC(g, c->d_ext_heavy, c->cap_reads);
+    DALLOC(g, c->d_ext_st, c->cap_reads); DALLOC(g, c->d_ext_jlist, c->cap_reads); DALLOC(g, c->d_ext_jkey, c->cap_reads); DALLOC(g, c->d_ext_jorder, c->cap_reads); DALLOC(g, c->d_ext_jobs, 1);
+    DALLOC(g, c->d_ext_jobs2, 1); DALLOC(g, c->d_ext_long, ExtLongLists::ints((size_t)c->cap_reads));
     return LH_OK;
 }
 
 static int rfa_alloc(lh_context* c) {
     i64 N = c->cap_reads;
-    { int rc = alloc_result_cols(c, PER_READ, N); if (rc) return rc; }   // the per-read columns of the result (DInf's)
+    DevGroup& g = c->mem;
+    { int rc = alloc_result_cols(c, g, PER_READ, N); if (rc) return rc; }   // the per-read columns of the result (DInf's)
     int want = c->co.rfa_grid;   // 16 single-wave blocks per CU = 4 waves per SIMD
     c->grid_rfa = c->cap_bc < want ? (int)c->cap_bc : want;
     c->slab_bytes = (i64)c->co.rfa_slab_kb << 10;
-    DALLOC(c->d_slab, (size_t)c->grid_rfa * (size_t)c->slab_bytes);
+    DALLOC(g, c->d_slab, (size_t)c->grid_rfa * (size_t)c->slab_bytes);
     // second-chance slabs for barcodes that outgrow the regular ones (up to the reader's 30,000-pair work units)
     // (a 30,000-pair barcode holds 60,000 reads; its molecule x read table is the large one: 1.5 GB = 6,000 molecules)
     c->slab2_bytes = (i64)c->cap_reads * 2048 + ((i64)16 << 20);
     c->grid_rfa2 = 4;
     if (c->slab2_bytes > ((i64)512 << 20)) { c->grid_rfa2 = 2; if (c->slab2_bytes > ((i64)1536 << 20)) c->slab2_bytes = (i64)1536 << 20; }
-    DALLOC(c->d_slab2, (size_t)c->grid_rfa2 * (size_t)c->slab2_bytes);
+    DALLOC(g, c->d_slab2, (size_t)c->grid_rfa2 * (size_t)c->slab2_bytes);
     // (r05) between the two: the molecule x read table grows with the square of a barcode's size on repeat families (every candidate position a molecule), and the step from 4,096
     // waves to 4 was a cliff — 2,000 barcodes of 200 pairs on the copies of repeat families, which outgrow 2 MiB, took 38 s instead of 0.1 s.  Up to 1,024 waves x 16 MiB, then
     // up to 64 x 128 MiB (tiers that would not be smaller than the last one are left out: small contexts).  (r06) The tiers' slabs are allocated when a batch first lists a
@@ -637,23 +592,18 @@ static int rfa_alloc(lh_context* c) {
             c->grid_rfa_mid_max[k] = c->cap_bc < gk ? (int)c->cap_bc : (int)gk;
         }
     }
-    DALLOC(c->d_rfa_ovf_mid, 4 * ((size_t)c->cap_bc + 1));   // the tiers' overflow lists (two for k_rfa, two for k_rfa_post)
-    DALLOC(c->d_bc_next, 24);   // (rfa_run)
-    DALLOC(c->d_rfa_ovf, c->cap_bc + 1); DALLOC(c->d_rfa_ovf2, c->cap_bc + 1); DALLOC(c->d_rfa_order, 3 * ((size_t)c->cap_bc + 4) + 4);
-    DALLOC(c->d_rfa_hp, N / 2 + 1); DALLOC(c->d_rfa_hr, 2 * N + 2); DALLOC(c->d_bc_lmp, c->cap_bc + 1);
+    DALLOC(g, c->d_rfa_ovf_mid, RfaOvfMid::ints((size_t)c->cap_bc));
+    DALLOC(g, c->d_bc_next, 1);
+    DALLOC(g, c->d_rfa_ovf, c->cap_bc + 1); DALLOC(g, c->d_rfa_ovf2, c->cap_bc + 1); DALLOC(g, c->d_rfa_order, RfaOrder::ints((size_t)c->cap_bc));
+    DALLOC(g, c->d_rfa_hp, N / 2 + 1); DALLOC(g, c->d_rfa_hr, 2 * N + 2); DALLOC(g, c->d_bc_lmp, c->cap_bc + 1);
     return LH_OK;
-}
-
-static void rfa_free(lh_context* c) {
-    free_result_cols(c, PER_READ);
-    hipFree(c->d_slab); hipFree(c->d_slab2); hipFree(c->d_slab_mid[0]); hipFree(c->d_slab_mid[1]); hipFree(c->d_rfa_ovf_mid); hipFree(c->d_rfa_ovf); hipFree(c->d_rfa_order); hipFree(c->d_bc_next); hipFree(c->d_rfa_ovf2); hipFree(c->d_rfa_hp); hipFree(c->d_rfa_hr); hipFree(c->d_bc_lmp);
 }
 
 // the length of an overflow list, read back by a one-thread kernel into mapped host memory (not a copy-engine transfer: those may be busy with the previous result)
 static int rfa_list_len(lh_context* c, const int32_t* count, i64* n) {
-    LH_LAUNCH(k_peek_i32, 1, 1, c->stream, count, c->h_peek + 5);
+    LH_LAUNCH(k_peek_i32, 1, 1, c->stream, count, &c->h_peek->rfa_listed);
     HIPCHK(hipStreamSynchronize(c->stream));
-    *n = c->h_peek[5];
+    *n = c->h_peek->rfa_listed;
     return LH_OK;
 }
 // tier k has slabs for a list of `listed` barcodes: as many as the list is long (a wave per slab takes the barcodes off the list one by one, so fewer only cost time),
@@ -663,18 +613,17 @@ static int rfa_tier_slabs(lh_context* c, int k, i64 listed, bool a_slab_each = f
     if (want < 1) want = 1;
     // (a_slab_each: the barcodes routed to the tier up front are a batch's largest — two of them in turn on one wave is the launch's duration doubled)
     if (c->d_slab_mid[k] && want <= (a_slab_each ? 1 : 2) * (i64)c->grid_rfa_mid[k]) return LH_OK;
-    if (c->d_slab_mid[k]) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->d_slab_mid[k]); c->d_slab_mid[k] = nullptr; c->grid_rfa_mid[k] = 0; }
+    if (c->d_slab_mid[k]) { HIPCHK(hipStreamSynchronize(c->stream)); c->tier_mem[k].release(); c->grid_rfa_mid[k] = 0; }
     i64 gk = want + want / 2 + 4;
     gk = gk > c->grid_rfa_mid_max[k] ? c->grid_rfa_mid_max[k] : gk;
-    DALLOC(c->d_slab_mid[k], (size_t)gk * (size_t)c->slab_mid_bytes[k]);
+    DALLOC(c->tier_mem[k], c->d_slab_mid[k], (size_t)gk * (size_t)c->slab_mid_bytes[k]);
     c->grid_rfa_mid[k] = (int)gk;
     return LH_OK;
 }
 
 static int rfa_run(lh_context* c, const DOpts& o, int& t) {
-    // [0] work counter of k_rfa, [1] its overflow count, [2] work counter of its last launch, [3] heavy pairs, [4] heavy reads, [5] work counter of k_rfa_post,
-    // [6] its overflow count, [7] work counter of its last launch; [8 + 4k ..]: tier k's work counter and overflow count, for k_rfa and for k_rfa_post
-    HIPCHK(hipMemsetAsync(c->d_bc_next, 0, 24 * sizeof(int32_t), c->stream));
+    RfaCounters* const ctr = c->d_bc_next;
+    HIPCHK(hipMemsetAsync(ctr, 0, sizeof(RfaCounters), c->stream));
     T_BEGIN("k_rfa");
     const int N = c->n_reads, P = c->n_pairs;
     // the wave kernels' scratch: the barcode program's slabs while they fit a pair's lists and Go's generator state (a context made with tiny slabs: the large ones)
@@ -683,42 +632,40 @@ static int rfa_run(lh_context* c, const DOpts& o, int& t) {
     const i64 wslab_bytes = small_ok ? c->slab_bytes : c->slab2_bytes;
     const int wgrid = small_ok ? c->grid_rfa : c->grid_rfa2;
     LH_LAUNCH(k_rfa_init, 4096, 256, c->stream, N, c->R, c->S, c->cand_cap);
-    LH_LAUNCH(k_rfa_tag, (P + 255) / 256, 256, c->stream, o, P, (const u64*)c->d_name_seed, c->R, c->S, c->cand_cap, c->d_rfa_hp, c->d_bc_next + 3);
-    LH_LAUNCH(k_rfa_tag_w, wgrid, 64, c->stream, o, (const u64*)c->d_name_seed, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hp, (const int32_t*)(c->d_bc_next + 3), c->d_status);
+    LH_LAUNCH(k_rfa_tag, (P + 255) / 256, 256, c->stream, o, P, (const u64*)c->d_name_seed, c->R, c->S, c->cand_cap, c->d_rfa_hp, &ctr->heavy_pairs);
+    LH_LAUNCH(k_rfa_tag_w, wgrid, 64, c->stream, o, (const u64*)c->d_name_seed, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hp, (const int32_t*)&ctr->heavy_pairs, c->d_status);
     int g = c->n_bc < c->grid_rfa ? c->n_bc : c->grid_rfa;
     // a barcode that does not fit a tier's slab is listed for the next: fewer waves, larger slabs; only the last one's verdict is final.  (r06) The host looks at a list's
     // length before it launches the tier that takes it (one small read-back; nothing is launched for an empty list — the usual batch) and makes sure the tier has slabs
     // (rfa_tier_slabs).
     // (r06) most candidates first; the barcodes whose tables cannot fit a regular slab apart (k_rfa_order)
-    int32_t* const ord_all = c->d_rfa_order;
-    int32_t* const ord_big = c->d_rfa_order + ((size_t)c->cap_bc + 4);
-    int32_t* const ord_rest = c->d_rfa_order + 2 * ((size_t)c->cap_bc + 4);
-    int32_t* const ord_cnt = c->d_rfa_order + 3 * ((size_t)c->cap_bc + 4);
-    LH_LAUNCH(k_rfa_order, 1, 256, c->stream, c->n_bc, (const int32_t*)c->d_bc_pair_off, c->R, ord_all, ord_big, ord_rest, ord_cnt, c->slab_bytes, c->idx->d.n_contigs + 2);
+    const RfaOrder ord(c->d_rfa_order, (size_t)c->cap_bc);
+    const RfaOvfMid ovf_mid(c->d_rfa_ovf_mid, (size_t)c->cap_bc);
+    LH_LAUNCH(k_rfa_order, 1, 256, c->stream, c->n_bc, (const int32_t*)c->d_bc_pair_off, c->R, ord.all, ord.big, ord.rest, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
     {
         // the first tier has slabs (an earlier batch needed them): the barcodes that cannot fit a regular slab start there at once, on a second stream, beside the first launch;
         // what they leave goes to the list the tier's own launch leaves its overflow in.  No slabs yet: the first launch sees every barcode and turns those away, as before
         const bool pre = c->slab_mid_bytes[0] && c->d_slab_mid[0] && c->grid_rfa_mid[0] > 0;
-        const int32_t *wl = pre ? ord_rest : ord_all, *wc = pre ? ord_cnt + 2 : ord_cnt;
-        int32_t *ol = c->d_rfa_ovf, *oc = c->d_bc_next + 1;
+        const int32_t *wl = pre ? ord.rest : ord.all, *wc = pre ? ord.n_rest : ord.n_all;
+        int32_t *ol = c->d_rfa_ovf, *oc = &ctr->n_ovf;
         if (pre) {
             HIPCHK(hipEventRecord(c->ev_fork, c->stream));
             HIPCHK(hipStreamWaitEvent(c->aux[0], c->ev_fork, 0));
             LH_LAUNCH(k_rfa, c->grid_rfa_mid[0], 64, c->aux[0], c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab_mid[0], c->slab_mid_bytes[0], c->d_status, c->d_bc_next + 16, (const int32_t*)ord_big, (const int32_t*)(ord_cnt + 1),
-                      c->d_rfa_ovf_mid, c->d_bc_next + 8 + 1, c->d_rfa_hr, c->d_bc_next + 4, c->d_bc_lmp);
+                      c->d_slab_mid[0], c->slab_mid_bytes[0], c->d_status, &ctr->routed_next, (const int32_t*)ord.big, (const int32_t*)ord.n_big,
+                      ovf_mid.rfa[0], &ctr->tier[0].n_ovf, c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
             HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
         }
         LH_LAUNCH(k_rfa, g, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap, c->d_slab,
-                  c->slab_bytes, c->d_status, c->d_bc_next, wl, wc, ol, oc, c->d_rfa_hr, c->d_bc_next + 4, c->d_bc_lmp);
+                  c->slab_bytes, c->d_status, &ctr->next, wl, wc, ol, oc, c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
         if (pre) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
         i64 listed = 0;
-        LH_LAUNCH(k_peek_i32, 1, 1, c->stream, (const int32_t*)(ord_cnt + 1), c->h_peek + 6);   // (read with the list's length below: one synchronisation)
+        LH_LAUNCH(k_peek_i32, 1, 1, c->stream, (const int32_t*)ord.n_big, &c->h_peek->rfa_routed);   // (read with the list's length below: one synchronisation)
         { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
-        const i64 n_routed = c->h_peek[6];
+        const i64 n_routed = c->h_peek->rfa_routed;
         int k_first = 0;
         if (pre && listed == 0) {   // nothing for the first tier's own launch: what the routed barcodes left there is the next tier's list
-            ol = c->d_rfa_ovf_mid; oc = c->d_bc_next + 8 + 1;
+            ol = ovf_mid.rfa[0]; oc = &ctr->tier[0].n_ovf;
             { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
             k_first = 1;
         }
@@ -726,100 +673,46 @@ static int rfa_run(lh_context* c, const DOpts& o, int& t) {
             if (!c->slab_mid_bytes[k]) continue;
             { int rc = rfa_tier_slabs(c, k, listed); if (rc) return rc; }
             wl = ol; wc = oc;
-            ol = c->d_rfa_ovf_mid + (size_t)k * ((size_t)c->cap_bc + 1); oc = c->d_bc_next + 8 + 4 * k + 1;
+            ol = ovf_mid.rfa[k]; oc = &ctr->tier[k].n_ovf;
             LH_LAUNCH(k_rfa, c->grid_rfa_mid[k], 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab_mid[k], c->slab_mid_bytes[k], c->d_status, c->d_bc_next + 8 + 4 * k, wl, wc, ol, oc, c->d_rfa_hr, c->d_bc_next + 4, c->d_bc_lmp);
+                      c->d_slab_mid[k], c->slab_mid_bytes[k], c->d_status, &ctr->tier[k].next, wl, wc, ol, oc, c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
             { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
         }
         if (listed > 0)
             LH_LAUNCH(k_rfa, c->grid_rfa2, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab2, c->slab2_bytes, c->d_status, c->d_bc_next + 2, (const int32_t*)ol, (const int32_t*)oc, (int32_t*)nullptr, (int32_t*)nullptr,
-                      c->d_rfa_hr, c->d_bc_next + 4, c->d_bc_lmp);
+                      c->d_slab2, c->slab2_bytes, c->d_status, &ctr->last_next, (const int32_t*)ol, (const int32_t*)oc, (int32_t*)nullptr, (int32_t*)nullptr,
+                      c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
         // the next batch's routed barcodes each want a slab of the first tier: as many as this batch routed (the tier grows when that is more than twice what it has)
         if (c->slab_mid_bytes[0] && n_routed > 0) { int rc = rfa_tier_slabs(c, 0, n_routed, true); if (rc) return rc; }
     }
     LH_LAUNCH(k_rfa_mq_w, wgrid, 64, c->stream, o, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hr,
-              (const int32_t*)(c->d_bc_next + 4), (const double*)c->d_bc_lmp, c->d_status);
+              (const int32_t*)&ctr->heavy_reads, (const double*)c->d_bc_lmp, c->d_status);
     {
-        const int32_t *wl = ord_all, *wc = ord_cnt;
-        int32_t *ol = c->d_rfa_ovf2, *oc = c->d_bc_next + 6;
+        const int32_t *wl = ord.all, *wc = ord.n_all;
+        int32_t *ol = c->d_rfa_ovf2, *oc = &ctr->post_n_ovf;
         LH_LAUNCH(k_rfa_post, g, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, c->cand_cap, c->d_slab, c->slab_bytes,
-                  c->d_status, c->d_bc_next + 5, wl, wc, ol, oc);
+                  c->d_status, &ctr->post_next, wl, wc, ol, oc);
         i64 listed = 0;
         { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
         for (int k = 0; k < 2 && listed > 0; ++k) {
             if (!c->slab_mid_bytes[k]) continue;
             { int rc = rfa_tier_slabs(c, k, listed); if (rc) return rc; }
             wl = ol; wc = oc;
-            ol = c->d_rfa_ovf_mid + (size_t)(2 + k) * ((size_t)c->cap_bc + 1); oc = c->d_bc_next + 8 + 4 * k + 3;
+            ol = ovf_mid.post[k]; oc = &ctr->tier[k].post_n_ovf;
             LH_LAUNCH(k_rfa_post, c->grid_rfa_mid[k], 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab_mid[k], c->slab_mid_bytes[k], c->d_status, c->d_bc_next + 8 + 4 * k + 2, wl, wc, ol, oc);
+                      c->d_slab_mid[k], c->slab_mid_bytes[k], c->d_status, &ctr->tier[k].post_next, wl, wc, ol, oc);
             { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
         }
         if (listed > 0)
             LH_LAUNCH(k_rfa_post, c->grid_rfa2, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, c->cand_cap, c->d_slab2,
-                      c->slab2_bytes, c->d_status, c->d_bc_next + 7, (const int32_t*)ol, (const int32_t*)oc, (int32_t*)nullptr, (int32_t*)nullptr);
+                      c->slab2_bytes, c->d_status, &ctr->post_last_next, (const int32_t*)ol, (const int32_t*)oc, (int32_t*)nullptr, (int32_t*)nullptr);
     }
     T_END();
 #ifdef LH_RFA_PROF
-    {
-        static const char* const names[15] = {"(k_rfa_init)", "  sort: loop head + lists of up to 64", "  probability sums: the reads' sums", "carve + contig grouping", "position sort", "inferMolecules + markBest step 1",
-                                               "scrapMolecules + markBest step 2", "optimizer", "moleculeMapqProbabilitySums (the sinks' scores)", "molecule status + penalty", "mate links + lists",
-                                               "estimateMapQualities (lane per read)", "(k_rfa_mq_w)", "(k_rfa_post)", "(k_rfa_post)"};
-        unsigned long long h[24];
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(lh_rfa_prof), sizeof h));
-        unsigned long long tot = 0;
-        for (int i = 0; i < 24; ++i) tot += h[i];
-        fprintf(stderr, "[lh] k_rfa phases (shader clocks summed over waves, %d barcodes):\n", c->n_bc);
-        for (int i = 0; i < 15; ++i) fprintf(stderr, "[lh]   %-44s %6.2f %%  %10.1f k clocks per barcode\n", names[i], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, (double)h[i] / 1e3 / (c->n_bc ? c->n_bc : 1));
-        {   // parts of the two phases above, when their markers are compiled in (their clocks are NOT in the phase's own line then)
-            static const char* const sub[8] = {"  inferMolecules", "  step 1: staging a tile", "  step 1: the entries of a tile", "  sort: network", "  sort: tie check + copy", "  sort: Go's algorithm on ranks", "  sort: smallest position", "  sort: keys"};
-            for (int i = 16; i < 24; ++i) if (h[i]) fprintf(stderr, "[lh]   %-44s %6.2f %%  %10.1f k clocks per barcode\n", sub[i - 16], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, (double)h[i] / 1e3 / (c->n_bc ? c->n_bc : 1));
-        }
-        memset(h, 0, sizeof h);
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_rfa_prof), h, sizeof h));
-    }
+    { int rc = prof_rfa(c); if (rc) return rc; }
 #endif
 #ifdef LH_RA_HIST
-    {
-        unsigned long long hh[40];
-        HIPCHK(hipStreamSynchronize(c->stream));
-        {
-            int32_t bn[24];
-            HIPCHK(hipMemcpy(bn, c->d_bc_next, sizeof bn, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[lh] k_rfa tiers: %d barcodes; listed for the 16 MiB tier %d (of %d waves), for the 128 MiB tier %d (of %d), for the last launch %d; k_rfa_post: %d / %d / %d\n", c->n_bc, bn[1],
-                    c->grid_rfa_mid[0], c->grid_rfa_mid[0] ? bn[9] : 0, c->grid_rfa_mid[1], c->grid_rfa_mid[1] ? bn[13] : (c->grid_rfa_mid[0] ? bn[9] : bn[1]), bn[6], bn[11], bn[15]);
-        }
-        HIPCHK(hipMemcpyFromSymbol(hh, HIP_SYMBOL(lh_rfa_hist), sizeof hh));
-        fprintf(stderr, "[lh] k_rfa, time per barcode (longest %.3f ms, sum %.1f ms over %d barcodes):", (double)hh[32] / 1e5, (double)hh[33] / 1e5, c->n_bc);
-        for (int b = 0; b < 32; ++b) if (hh[b]) fprintf(stderr, " <%.4g ms: %llu", (double)(2ull << b) / 1e5, hh[b]);
-        {
-            unsigned long long nb = 0;
-            for (int b = 0; b < 32; ++b) nb += hh[b];
-            if (nb) fprintf(stderr, "; per finished barcode: %.0f candidates (%.0f filtered), %.0f molecules, carve %.0f KB, molecule x read table %.0f K words", (double)hh[34] / nb, (double)hh[35] / nb,
-                            (double)hh[36] / nb, (double)hh[37] / nb / 1024.0, (double)hh[38] / nb / 1024.0);
-        }
-        fprintf(stderr, "\n");
-        memset(hh, 0, sizeof hh);
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_rfa_hist), hh, sizeof hh));
-        {
-            unsigned long long h2[8];
-            HIPCHK(hipMemcpyFromSymbol(h2, HIP_SYMBOL(lh_rfa_hist2), sizeof h2));
-            fprintf(stderr, "[lh] k_rfa position sort (large barcodes): %llu contig lists, longest %llu, longer than %d: %llu, longer than %d: %llu, with two equal positions: %llu, sum of squares %.3g\n", h2[0], h2[1],
-                    LH_RFA_SORT_LDS, h2[2], LH_RFA_LDS_BYTES / 4, h2[3], h2[5], (double)h2[4]);
-            memset(h2, 0, sizeof h2);
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_rfa_hist2), h2, sizeof h2));
-            static int bs[4096][8];
-            HIPCHK(hipMemcpyFromSymbol(bs, HIP_SYMBOL(lh_rfa_bcstat), sizeof bs));
-            std::vector<int> ord(4096);
-            for (int i = 0; i < 4096; ++i) ord[i] = i;
-            std::sort(ord.begin(), ord.end(), [&](int x, int y) { return bs[x][0] > bs[y][0]; });
-            for (int k = 0; k < 6; ++k) { const int* b = bs[ord[k == 5 ? 2000 : k]]; fprintf(stderr, "[lh]   %s barcode: %.2f ms, %d candidates (%d filtered), %d raw molecules (largest %d), %d contigs (longest list %d), %d molecules\n", k == 5 ? "a median" : "slow", b[0] / 1e5, b[1], b[2], b[3], b[4], b[5], b[7], b[6]); }
-            memset(bs, 0, sizeof bs);
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_rfa_bcstat), bs, sizeof bs));
-        }
-    }
+    { int rc = hist_rfa(c); if (rc) return rc; }
 #endif
     c->ran_inference = true;
     return LH_OK;

@@ -165,3 +165,31 @@ void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
     }
 }
 }  // namespace emu
+
+// ---- device memory ---------------------------------------------------------------------------------
+#include <mutex>
+#include <unordered_set>
+namespace emu {
+static std::mutex alloc_mu;
+static std::unordered_set<void*> live;
+static long long n_calls = 0, fail_in = 0, n_bad_frees = 0;
+hipError_t dev_malloc(void** p, size_t n) {
+    std::lock_guard<std::mutex> g(alloc_mu);
+    ++n_calls;
+    if (fail_in > 0 && --fail_in == 0) { *p = nullptr; return 2; }
+    *p = n ? aligned_alloc(256, (n + 255) / 256 * 256) : nullptr;
+    if (*p) live.insert(*p);
+    return (n && !*p) ? 2 : 0;
+}
+hipError_t dev_free(void* p) {
+    if (!p) return 0;
+    std::lock_guard<std::mutex> g(alloc_mu);
+    if (!live.erase(p)) { ++n_bad_frees; return 1; }
+    free(p);
+    return 0;
+}
+long long alloc_live() { std::lock_guard<std::mutex> g(alloc_mu); return (long long)live.size(); }
+long long alloc_calls() { std::lock_guard<std::mutex> g(alloc_mu); return n_calls; }
+long long alloc_bad_frees() { std::lock_guard<std::mutex> g(alloc_mu); return n_bad_frees; }
+void alloc_fail_at(long long k) { std::lock_guard<std::mutex> g(alloc_mu); fail_in = k; }
+}  // namespace emu

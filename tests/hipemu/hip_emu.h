@@ -163,9 +163,20 @@ struct EmuEvent { std::chrono::steady_clock::time_point t; };
 typedef EmuEvent* hipEvent_t;
 #define hipSuccess 0
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = n ? aligned_alloc(256, (n + 255) / 256 * 256) : nullptr; return (n && !*p) ? 2 : 0; }
+// device memory (hip_emu.cpp): aligned_alloc / free, with a book of the live allocations for the tests (emu_lib.cpp exports the numbers).  A test can make the
+// k-th hipMalloc from now fail (an error, nothing allocated); a hipFree of an address that is not live — a second free, a stale pointer — is counted and
+// does not reach free()
+namespace emu {
+hipError_t dev_malloc(void** p, size_t n);
+hipError_t dev_free(void* p);
+long long alloc_live();        // device allocations that have not been freed
+long long alloc_calls();       // hipMalloc calls so far, failed ones included
+long long alloc_bad_frees();   // hipFree calls with an address that was not live
+void alloc_fail_at(long long k);   // k >= 1: the k-th hipMalloc from now fails, once; 0: none
+}  // namespace emu
+static inline hipError_t hipMalloc(void** p, size_t n) { return emu::dev_malloc(p, n); }
 template <class T> static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
-static inline hipError_t hipFree(void* p) { free(p); return 0; }
+static inline hipError_t hipFree(void* p) { return emu::dev_free(p); }
 #define hipHostMallocDefault 0
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
 static inline hipError_t hipHostFree(void* p) { free(p); return 0; }

@@ -590,3 +590,104 @@ def test_emu_context_moves_between_regimes(emu, oracle):
     for rs in (rs_rep, rs_uni, rs_rep2, rs_rep):
         b = helpers.batch_of(rs)
         helpers.assert_same_result(ctx.align_barcodes(b), oidx.align_barcodes(b, threads=8), inference=True)
+
+
+# ---- the device workspace's regrow paths and allocation failures (the `small` build: its seed and candidate pools start at LH_POOL_FLOOR = 64 entries,
+# tests/hipemu/Makefile; the emulator keeps a book of the device allocations, tests/hipemu/hip_emu.h)
+def _small_lib_with_alloc_book():
+    import ctypes
+    subprocess.check_call(["make", "-s", "-C", os.path.join(helpers.ROOT, "tests", "hipemu"), "small"])
+    lib = capi.Library(os.path.join(helpers.ROOT, "tests", "_build", "liblariat_emu_small.so"))
+    for f in ("emu_alloc_live", "emu_alloc_calls", "emu_alloc_bad_frees"):
+        getattr(lib.L, f).restype = ctypes.c_longlong
+    lib.L.emu_alloc_fail_at.argtypes = [ctypes.c_longlong]
+    lib.L.emu_alloc_fail_at.restype = None
+    return lib
+
+
+def _regrow_case(oracle):
+    """an index, a batch of a few pairs on unique sequence (fits a context's first pools) and one on repeat families (more than 16 seeds and 3 candidates per
+    read of the context's capacity: outgrows both), with the oracle's results"""
+    names, contigs, rs_rep = helpers.repeat_family_case(13, 2, pairs=6)
+    oidx = oracle.index_build_naive(names, contigs)
+    rs_uni = helpers.small_reads(names, contigs, n_barcodes=2, pairs=3, junk=0.0, seed=77)
+    batches = [helpers.batch_of(rs_uni), helpers.batch_of(rs_rep)]
+    refs = [oidx.align_barcodes(b, threads=8) for b in batches]
+    return oidx, max(rs_uni.n_pairs, rs_rep.n_pairs), batches, refs
+
+
+def test_emu_pools_regrow_on_demand(oracle):
+    """one context, a batch that fits the seed pools and the candidate pools it was created with, then one that outgrows both (stage2_run, run_front): each
+    result equals the oracle's, and the second batch did allocate both groups again"""
+    lib = _small_lib_with_alloc_book()
+    oidx, cap, batches, refs = _regrow_case(oracle)
+    idx = lib.index_from_arrays(oidx.arrays())
+    ctx = idx.context(cap)
+    calls = [lib.L.emu_alloc_calls()]
+    for b, ref in zip(batches, refs):
+        helpers.assert_same_result(ctx.align_barcodes(b), ref, inference=True)
+        calls.append(lib.L.emu_alloc_calls())
+    n_reads = 2 * cap
+    assert refs[0].cand_off[-1] <= max(3 * n_reads, 64) < refs[1].cand_off[-1]   # the candidate pools' first size lies between the two batches' totals
+    # K6's job arrays (3 buffers) are the only allocation a batch inside the pools makes; the second batch adds the seed pools (15) and the candidate pools
+    # (4 + the 3 pack buffers + 12 + the per-candidate result columns, more than 20 together)
+    assert calls[1] - calls[0] <= 3, calls
+    assert calls[2] - calls[1] >= 15 + 19 + 20, calls
+    assert lib.L.emu_alloc_bad_frees() == 0
+
+
+def test_emu_allocation_failure_sweep(oracle):
+    """every hipMalloc of a scenario fails in turn — context creation, the two batches of test_emu_pools_regrow_on_demand each aligned and downloaded, the
+    creation of a two-lane context.  The failing call returns an error with a message; the same call again on the same context succeeds with the oracle's result
+    (or fails again); nothing is freed twice; and lh_context_free returns every device allocation the context made."""
+    lib = _small_lib_with_alloc_book()
+    oidx, cap, batches, refs = _regrow_case(oracle)
+    idx = lib.index_from_arrays(oidx.arrays())
+    opts = lib.opts()
+    L = lib.L
+
+    struck = []
+
+    def attempt(call):
+        """a call of the scenario; when the injected failure strikes it, the error must be reported, and the same call is made again: (done, its value)"""
+        try:
+            return True, call()
+        except capi.LhError as e:
+            assert e.code != 0 and L.lh_last_error() != b"", e
+            struck.append(e)
+        try:
+            return True, call()
+        except capi.LhError:
+            return False, None
+
+    def scenario():   # (once the failure has struck and its batch is done, what follows would be the unfailed run again: left out)
+        del struck[:]
+        made, ctx = attempt(lambda: idx.context(cap))
+        if made:
+            for b, ref in zip(batches, refs):
+                if struck:
+                    break
+                done = attempt(lambda: ctx.upload(b))[0] and attempt(lambda: ctx.align_resident(opts))[0]
+                done, res = attempt(ctx.download) if done else (False, None)
+                if not done:
+                    break
+                helpers.assert_same_result(res, ref, inference=True)
+            ctx.close()
+        if made and struck:
+            return
+        made, two = attempt(lambda: idx.context(cap, lanes=2))
+        if made:
+            two.close()
+
+    live0, bad0 = L.emu_alloc_live(), L.emu_alloc_bad_frees()
+    c0 = L.emu_alloc_calls()
+    scenario()
+    m = L.emu_alloc_calls() - c0
+    assert m > 300, m   # (a context makes ~130 allocations, the second batch's regrows ~60)
+    assert L.emu_alloc_live() == live0
+    for k in range(1, m + 1):
+        L.emu_alloc_fail_at(k)
+        scenario()
+        L.emu_alloc_fail_at(0)
+        assert L.emu_alloc_bad_frees() == bad0, k
+        assert L.emu_alloc_live() == live0, (k, L.emu_alloc_live() - live0)
