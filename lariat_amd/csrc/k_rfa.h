@@ -127,6 +127,37 @@ __device__ __forceinline__ double dev_pseudo_score(const DCand& R, i64 a, double
     return score;
 }
 
+// The map quality of one alignment (lariat.go:971-989) from its pair score, the read's total_probability (the sum of 10^score over the read's
+// LH_MAPQ_TOP best scores), its sum_move_probability_change and whether it lies in its contig's centromere: min(60, pair term, molecule term),
+// truncated; NaN (a single score above every pair score) gives INT_MIN as Go's int(NaN) does.  Both forms of estimateMapQualities end here.
+// LH_MAPQ_WEAK (test builds only, tests/hipemu `mapqweak1` .. `mapqweak4`) makes it wrong by less than a unit on most alignments — 1: rounds to nearest,
+// 2: pow / log10 in float, 3: total_probability over 16 scores, 4: no molecule term — and tests/test_mapq.py must see each of them fail.
+#ifndef LH_MAPQ_WEAK
+#define LH_MAPQ_WEAK 0
+#endif
+#define LH_MAPQ_TOP (LH_MAPQ_WEAK == 3 ? 16 : 15)
+__device__ __forceinline__ double dev_mapq_pow10(double x) { return LH_MAPQ_WEAK == 2 ? (double)powf(10.0f, (float)x) : pow(10.0, x); }
+__device__ __forceinline__ int dev_mapq(double score, double total, double sum_move, int in_centromere) {
+    double mapq = -10.0 * log10(1.0 - pow(10.0, score) / total);
+    double mmq = -10.0 * log10(1.0 - (1.0 / sum_move));
+    if (LH_MAPQ_WEAK == 2) {   // the two terms as a float kernel would write them
+        mapq = (double)(-10.0f * log10f(1.0f - powf(10.0f, (float)score) / (float)total));
+        mmq = (double)(-10.0f * log10f(1.0f - 1.0f / (float)sum_move));
+    }
+    if (LH_MAPQ_WEAK == 4) mmq = mapq;
+    mapq = (mapq != mapq || mmq != mmq) ? mapq + mmq : (mapq < mmq ? mapq : mmq);   // math.Min propagates NaN
+    mapq = (mapq != mapq) ? mapq : (60.0 < mapq ? 60.0 : mapq);
+    if (in_centromere) mapq = 0.0;
+    if (LH_MAPQ_WEAK == 1) mapq += 0.5;
+    return (mapq != mapq) ? (int)0x80000000 : (int)mapq;
+}
+// lariat.go:981-986: the alignment starts inside its contig's centromere
+__device__ __forceinline__ int dev_in_centromere(const DCand& R, const i64* __restrict__ cen_start, const i64* __restrict__ cen_end, i64 a) {
+    i64 cs = -1, ce = -1;
+    if (R.rid[a] >= 0 && cen_start[R.rid[a]] >= 0) { cs = cen_start[R.rid[a]]; ce = cen_end[R.rid[a]]; }
+    return R.pos[a] > cs && R.pos[a] <= ce;
+}
+
 struct RfaTab {   // carved from the wave's slab
     int32_t* plist;      // [NCf] local candidate ids
     int32_t* molraw;     // [NCf] raw molecule id of plist entry
@@ -181,7 +212,7 @@ __device__ __forceinline__ int dev_mol_active(int alen, int nbest, int change) {
 #endif
 #define LH_RFA_LDS_BYTES (LH_RFA_SORT_LDS * 12)
 
-static_assert(LH_RFA_LDS_BYTES >= 15 * 64 * (int)sizeof(double), "estimateMapQualities keeps a read's top-15 scores per lane in lds_raw (top[k * 64 + lane])");
+static_assert(LH_RFA_LDS_BYTES >= LH_MAPQ_TOP * 64 * (int)sizeof(double), "estimateMapQualities keeps a read's top-15 scores per lane in lds_raw (top[k * 64 + lane])");
 #define LH_RFA_NCONT_LDS 1024  // contig slots of a barcode kept in LDS while grouping (index with more contigs: slab copy)
 #define LH_RFA_SRC_CHUNK 256   // source-molecule alignments staged per pass of fastScore
 #ifndef LH_RFA_MOL_LDS_MIN
@@ -1389,9 +1420,9 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
 #define TOP_PUSH(v_)                                                                   \
     {                                                                                  \
         double v = (v_);                                                               \
-        int k_ = ntop < 15 ? ntop : 15;                                                \
-        if (ntop < 15 || v > TOPV(14)) {                                               \
-            if (ntop < 15) ntop++; else k_ = 14;                                       \
+        int k_ = ntop < LH_MAPQ_TOP ? ntop : LH_MAPQ_TOP;                              \
+        if (ntop < LH_MAPQ_TOP || v > TOPV(LH_MAPQ_TOP - 1)) {                         \
+            if (ntop < LH_MAPQ_TOP) ntop++; else k_ = LH_MAPQ_TOP - 1;                 \
             while (k_ > 0 && TOPV(k_ - 1) < v) { TOPV(k_) = TOPV(k_ - 1); k_--; }      \
             TOPV(k_) = v;                                                              \
         }                                                                              \
@@ -1432,18 +1463,10 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             S.second_best_idx[gr] = sb_aln; S.second_best_score[gr] = sb_raw;
             S.as_score[gr] = dev_score_aln(R, S, improper, act, S.mate[act], 0.0);
             double total = 0;
-            for (int k = 0; k < ntop; ++k) total += pow(10.0, TOPV(k));
+            for (int k = 0; k < ntop; ++k) total += dev_mapq_pow10(TOPV(k));
             for (i64 a = a0; a < a1; ++a) {
                 if (!R.in_filtered[a]) continue;
-                double score = dev_score_aln(R, S, improper, a, S.mate[a], lmp);
-                double mapq = -10.0 * log10(1.0 - pow(10.0, score) / total);
-                double mmq = -10.0 * log10(1.0 - (1.0 / S.sum_move[a]));
-                mapq = (mapq != mapq || mmq != mmq) ? mapq + mmq : (mapq < mmq ? mapq : mmq);   // math.Min propagates NaN
-                mapq = (mapq != mapq) ? mapq : (60.0 < mapq ? 60.0 : mapq);
-                i64 cs = -1, ce = -1;
-                if (R.rid[a] >= 0 && cen_start[R.rid[a]] >= 0) { cs = cen_start[R.rid[a]]; ce = cen_end[R.rid[a]]; }
-                if (R.pos[a] > cs && R.pos[a] <= ce) mapq = 0.0;
-                S.mapq[a] = (mapq != mapq) ? (int)0x80000000 : (int)mapq;
+                S.mapq[a] = dev_mapq(dev_score_aln(R, S, improper, a, S.mate[a], lmp), total, S.sum_move[a], dev_in_centromere(R, cen_start, cen_end, a));
             }
 #undef TOP_PUSH
 #undef TOPV
@@ -1574,7 +1597,7 @@ __global__ void __launch_bounds__(64) k_rfa_mq_w(DOpts o, const i64* __restrict_
             if (sb_aln < 0) sb_raw = pseudo;
             // the 15 best scores, largest first (sort.Float64s, then the last 15 from the top)
             double total = 0.0;
-            for (int k = 0; k < 15 && k < n_sc; ++k) {
+            for (int k = 0; k < LH_MAPQ_TOP && k < n_sc; ++k) {
                 double v = -1.7976931348623157e308;
                 int at = -1;
                 for (int i = lane; i < n_sc; i += 64) { const double x = sc_all[i]; if (x > v || (x == v && at < 0)) { v = x; at = i; } }
@@ -1583,7 +1606,7 @@ __global__ void __launch_bounds__(64) k_rfa_mq_w(DOpts o, const i64* __restrict_
                     const int oa = __shfl_xor(at, msk);
                     if (oa >= 0 && (at < 0 || ov > v || (ov == v && oa < at))) { v = ov; at = oa; }
                 }
-                total += pow(10.0, v);
+                total += dev_mapq_pow10(v);
                 WAVE_SYNC();
                 if (lane == 0) sc_all[at] = -1.7976931348623157e308;   // taken
                 WAVE_SYNC();
@@ -1595,15 +1618,7 @@ __global__ void __launch_bounds__(64) k_rfa_mq_w(DOpts o, const i64* __restrict_
             }
             for (i64 a = a0 + lane; a < a1; a += 64) {
                 if (!R.in_filtered[a]) continue;
-                double score = dev_score_aln(R, S, improper, a, S.mate[a], lmp);
-                double mapq = -10.0 * log10(1.0 - pow(10.0, score) / total);
-                double mmq = -10.0 * log10(1.0 - (1.0 / S.sum_move[a]));
-                mapq = (mapq != mapq || mmq != mmq) ? mapq + mmq : (mapq < mmq ? mapq : mmq);   // math.Min propagates NaN
-                mapq = (mapq != mapq) ? mapq : (60.0 < mapq ? 60.0 : mapq);
-                i64 cs = -1, ce = -1;
-                if (R.rid[a] >= 0 && cen_start[R.rid[a]] >= 0) { cs = cen_start[R.rid[a]]; ce = cen_end[R.rid[a]]; }
-                if (R.pos[a] > cs && R.pos[a] <= ce) mapq = 0.0;
-                S.mapq[a] = (mapq != mapq) ? (int)0x80000000 : (int)mapq;
+                S.mapq[a] = dev_mapq(dev_score_aln(R, S, improper, a, S.mate[a], lmp), total, S.sum_move[a], dev_in_centromere(R, cen_start, cen_end, a));
             }
             WAVE_SYNC();
     }

@@ -420,7 +420,8 @@ static void estimateMapQualities(Ctx& x, std::vector<std::vector<int>>& alignmen
         // lariat.go:963-968
         std::sort(scores.begin(), scores.end());
         double total_probability = 0;
-        for (int i = (int)scores.size() - 1; i >= 0 && (int)scores.size() - i <= 15; i--) total_probability += std::pow(10.0, scores[i]);
+        int n_terms = 0;
+        for (int i = (int)scores.size() - 1; i >= 0 && (int)scores.size() - i <= 15; i--) { total_probability += std::pow(10.0, scores[i]); ++n_terms; }
         for (int a : arr) {   // lariat.go:971-989
             Cand& A = x.c[a];
             double score = scoreAlignment(x, &A, A.mate_alignment >= 0 ? &x.c[A.mate_alignment] : nullptr, lmp);
@@ -432,6 +433,8 @@ static void estimateMapQualities(Ctx& x, std::vector<std::vector<int>>& alignmen
             int64_t start = -1, end = -1;
             if (cen_start && A.rid >= 0 && cen_start[A.rid] >= 0) { start = cen_start[A.rid]; end = cen_end[A.rid]; }
             if (A.pos > start && A.pos <= end) mapq = 0.0;
+            A.mq_set = true; A.mq_centromere = A.pos > start && A.pos <= end; A.mq_nterms = n_terms; A.mq_nscores = (int)scores.size();
+            A.mq_score = score; A.mq_total = total_probability; A.mq_raw = mapq;
             A.mapq = std::isnan(mapq) ? INT32_MIN : (int)mapq;   // Go int(NaN) on amd64 = MinInt64
         }
     }

@@ -53,6 +53,11 @@ struct Cand {
     double md_sb_molecule_confidence = 0;
     bool has_split_md = false;
     double split_second_best = 0, split_score = 0;
+    // what estimateMapQualities held when it wrote `mapq` (lariat.go:963-989): the pair score, total_probability, the number of scores summed
+    // into it and the number the read had, whether the centromere rule zeroed the value, and the double right before int().  Reporting only: nothing reads them back.
+    bool mq_set = false, mq_centromere = false;
+    int mq_nterms = 0, mq_nscores = 0;
+    double mq_score = 0, mq_total = 0, mq_raw = 0;
 };
 
 struct BarcodeResult {

@@ -28,6 +28,7 @@ struct ResultArena {
     std::vector<double> lap, mol_diff, mol_conf, sum_move, second_best_score, as_score, split_second_best, split_score;
     std::vector<int32_t> md_int;   // 7 per candidate: copies, in active, unique active, outside, reads in molecule, second best: molecule reads, proper
     std::vector<double> md_sb_conf;
+    std::vector<double> mq_terms;   // 8 per candidate, see lo_result_mapq_terms
 };
 
 struct DumpArena {
@@ -258,6 +259,7 @@ int lo_align_barcodes(const Index* idx, const lh_opts* opts, const lh_batch* b, 
             A->mate_idx.push_back(c.mate_alignment >= 0 ? base + c.mate_alignment : -1);
             for (int v : {c.md_copies, c.md_copies_in_active, c.md_unique_active, c.md_copies_outside, c.md_reads_in_molecule, c.md_sb_molecule_reads, (int)c.md_sb_proper}) A->md_int.push_back(v);
             A->md_sb_conf.push_back(c.md_sb_molecule_confidence);
+            for (double v : {(double)c.mq_set, c.mq_score, c.mq_total, (double)c.mq_nterms, c.sum_move_probability_change, (double)c.mq_centromere, c.mq_raw, (double)c.mq_nscores}) A->mq_terms.push_back(v);
             if (c.active) {
                 int64_t r = r0 + c.read_id;
                 A->active_idx[r] = base + (int64_t)i;
@@ -307,6 +309,15 @@ int lo_result_mapq_data(const lh_result* r, const int32_t** md_int, const double
     if (!r || !r->arena_ || !md_int || !md_sb_conf) { g_err = "lo_result_mapq_data: bad argument"; return LH_E_ARG; }
     ResultArena* A = (ResultArena*)r->arena_;
     *md_int = A->md_int.data(); *md_sb_conf = A->md_sb_conf.data();
+    return LH_OK;
+}
+
+// The terms of every MAPQ as estimateMapQualities held them when it wrote `mapq` (lariat.go:963-989), for a result of lo_align_barcodes: 8 doubles per
+// candidate — whether the candidate went through estimateMapQualities at all (in-filtered, inference on), the pair score, total_probability, the number
+// of scores summed into it, sum_move_probability_change, whether the centromere rule zeroed the value, the double `mapq` right before int(), and the number of scores the read had (the 15 largest are summed)
+int lo_result_mapq_terms(const lh_result* r, const double** terms) {
+    if (!r || !r->arena_ || !terms) { g_err = "lo_result_mapq_terms: bad argument"; return LH_E_ARG; }
+    *terms = ((ResultArena*)r->arena_)->mq_terms.data();
     return LH_OK;
 }
 

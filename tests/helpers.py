@@ -74,8 +74,148 @@ F64_FIELDS = ["log_alignment_probability", "molecule_difference", "molecule_conf
               "split_second_best", "split_score"]
 
 
+MAPQ_ULP = 2.0 ** -52
+MAPQ_ETA = 69 * MAPQ_ULP   # 1.53e-14, see mapq_reference
+MAPQ_P_ONE = 1e-7           # 1 - p in (-MAPQ_P_ONE, 0) is p = 1, see mapq_reference
+
+
+def _mapq_raw_decimal(score, total, sum_move, centromere, ctx):
+    """min(60, -10 log10(1 - 10^score / total), -10 log10(1 - 1 / sum_move)) of three Decimals; None for NaN (a logarithm of a negative number)"""
+    import decimal
+    D = decimal.Decimal
+    if centromere:
+        return D(0)
+    out = D(60)
+    for one_minus in (1 - ctx.divide(ctx.power(D(10), score), total), 1 - ctx.divide(D(1), sum_move)):
+        if -D(MAPQ_P_ONE) < one_minus < 0:
+            one_minus = D(0)
+        if one_minus < 0:
+            return None
+        if one_minus > 0:           # (0: -log10(0) = +Inf, the other term or the cap binds)
+            out = min(out, -10 * ctx.log10(one_minus))
+    return out
+
+
+def _trunc_mapq(x):
+    """Go's int(float64) as the product applies it: towards zero, NaN -> INT_MIN"""
+    return -2 ** 31 if x is None else int(x)
+
+
+def mapq_reference(terms, eta=MAPQ_ETA, screen=True):
+    """What the MAPQ of every candidate must be, from the terms the oracle held when it wrote it (oracle_py.MAPQ_TERMS: pair score, total_probability,
+    sum_move_probability_change, centromere), evaluated again in 50-digit decimal arithmetic:
+
+        raw = min(60, -10 log10(1 - 10^score / total), -10 log10(1 - 1 / sum_move)),   0 inside a centromere,   mapq = int(raw)   (NaN -> INT_MIN)
+
+    A correct double-precision implementation holds score, total and sum_move only to rounding noise, so for every candidate the closed interval of raw
+    values is computed that is reachable when each of the three moves by a relative eta (raw is monotone in each: rising in score, falling in total and
+    in sum_move; the ends are widened by a relative eta once more for the last logarithm).  A candidate is DECIDABLE when both ends truncate to the same
+    integer (both >= 60, both in (-1, 1) and both NaN included): there the product's MAPQ must equal it.  Elsewhere it must lie between the truncations
+    of the two ends.
+
+    eta is not the contract's 1e-9 for the float scores: it is the noise of evaluating the same double-precision expressions in another order with another
+    libm, counted in ulp (2^-52) with a rounded +, -, *, / at 0.5 ulp and, as no error table of the ROCm device library is at hand, the OpenCL
+    double-precision bounds for the functions, which are looser: log10 3 ulp, pow 16 ulp.
+      * the pair score (scoreAlignment, lariat.go:599-624): up to 8 additions of terms of one sign (4 ulp), one of them the log molecule penalty,
+        log10(dnaLength / genome_length * 0.05): a division, a multiplication (1 ulp, and less after the logarithm) and the log10 (3 ulp)          8    ulp
+      * total_probability: 14 additions of positive terms                                                                                    7    ulp
+      * the expression itself: one pow (16), one division (0.5), one log10 (3)                                                               19.5 ulp
+    34.5 ulp, times a safety factor of 2: eta = 69 ulp = 1.53e-14.  (The terms of sum_move_probability_change are pow's of sums of the same kind, summed
+    in the molecules' order: the same bound.)  What this buys: Lariat's penalties are whole or half log10 units, so raw values cluster 4.3e-6 below an
+    integer (-10 log10(1.000001e-6) = 59.9999957); there 1 - p ~ 1e-6 turns a relative eta' of p into 4.3e6 eta' of raw, and eta' = (|score| ln 10 + 2) eta
+    is 5e-13 at a pair score of -15: the cluster stays decidable by a factor of about 8 (tests/test_mapq.py prints the smallest factor of its workload; DESIGN.md
+    section 2 has the figure).  With the contract's 1e-9 in eta's place the same candidates are undecidable.
+
+    p = 1: an alignment whose own 10^score is one of the terms of total_probability has p <= 1 in every correct implementation (the terms are positive, a
+    rounded sum is not below its largest term), and p = 1 exactly when the other terms vanish beside it — every uniquely placed read.  The terms reported
+    here do not say whether the own term is in the sum, and 10^score evaluated afresh may exceed the reported total by a rounding error; so 1 - p in
+    (-1e-7, 0) counts as 0 (-log10(0) = +Inf: the cap or the molecule term binds).  A true NaN has 10^score above the total by a factor, not by 1e-7: the scores
+    lie on a lattice of half log10 units, and eta moves p by (|score| ln 10 + 2) eta < 1e-11.
+
+    `screen`: candidates whose interval, evaluated in double with 4096 eta in eta's place (which covers the double evaluation's own error: that is what eta
+    bounds), truncates to one integer at both ends are decided there and then; only the others (those within ~1e-7 of an integer) go through decimal.
+    screen=False sends all through decimal.
+
+    Returns a dict of arrays over all candidates: `set` (the candidate went through estimateMapQualities), `lo`, `hi` (the truncated ends), `decidable`,
+    `raw` (the decimal value as a float, NaN where screened or NaN), `margin` (distance of the decimal value to the next integer boundary over the
+    interval's half width; Inf where screened)."""
+    import decimal
+    ctx = decimal.Context(prec=50)
+    D = decimal.Decimal
+    t = np.asarray(terms, dtype=np.float64)
+    n = len(t)
+    isset = t[:, 0] != 0
+    lo, hi = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    raw, margin = np.full(n, np.nan), np.full(n, np.inf)
+    todo = isset.copy()
+    if screen and n:
+        w = 4096 * eta
+        sc, tot, sm, cen = t[:, 1], t[:, 2], t[:, 4], t[:, 5] != 0
+
+        def f(sc_, tot_, sm_):
+            with np.errstate(all="ignore"):
+                om = 1.0 - 10.0 ** sc_ / tot_
+                a = -10.0 * np.log10(np.where((om < 0) & (om > -MAPQ_P_ONE), 0.0, om))
+                om = 1.0 - 1.0 / sm_
+                b = -10.0 * np.log10(np.where((om < 0) & (om > -MAPQ_P_ONE), 0.0, om))
+                v = np.where(np.isnan(a) | np.isnan(b), np.nan, np.minimum(60.0, np.minimum(a, b)))
+            return np.where(cen, 0.0, v)
+
+        a_lo = f(sc * (1 + w), tot * (1 + w), sm * (1 + w))   # (score < 0: score (1 + w) is the lower one)
+        a_hi = f(sc * (1 - w), tot * (1 - w), sm * (1 - w))
+        with np.errstate(all="ignore"):
+            a_lo, a_hi = a_lo - np.abs(a_lo) * w, a_hi + np.abs(a_hi) * w
+            fine = isset & np.isfinite(a_lo) & np.isfinite(a_hi) & (sc <= 0) & (np.trunc(a_lo) == np.trunc(a_hi)) & (a_lo <= a_hi)
+        lo[fine] = hi[fine] = np.trunc(a_lo[fine]).astype(np.int64)
+        todo &= ~fine
+    for i in np.nonzero(todo)[0]:
+        sc, tot, sm, cen = D(float(t[i, 1])), D(float(t[i, 2])), D(float(t[i, 4])), t[i, 5] != 0
+        e = D(eta)
+        s_lo, s_hi = (sc * (1 + e), sc * (1 - e)) if sc < 0 else (sc * (1 - e), sc * (1 + e))
+        mid = _mapq_raw_decimal(sc, tot, sm, cen, ctx)
+        r_lo = _mapq_raw_decimal(s_lo, tot * (1 + e), sm * (1 + e), cen, ctx)
+        r_hi = _mapq_raw_decimal(s_hi, tot * (1 - e), sm * (1 - e), cen, ctx)
+        if r_lo is not None and r_lo < 60:
+            r_lo -= abs(r_lo) * e
+        if r_hi is not None and r_hi < 60:
+            r_hi += abs(r_hi) * e
+        ends = sorted([_trunc_mapq(r_lo), _trunc_mapq(r_hi), _trunc_mapq(mid)])   # (a NaN end: INT_MIN, below every value)
+        lo[i], hi[i] = ends[0], ends[-1]
+        if mid is not None:
+            raw[i] = float(mid)
+            if r_lo is not None and r_hi is not None and r_hi > r_lo and 0 < mid < 60:
+                margin[i] = float(min(mid - int(mid), int(mid) + 1 - mid) / ((r_hi - r_lo) / 2))
+    return dict(set=isset, lo=lo, hi=hi, decidable=isset & (lo == hi), raw=raw, margin=margin)
+
+
+def assert_mapq(mapq, ref, eta=MAPQ_ETA, screen=True):
+    """the product's MAPQ against the oracle result `ref` and its terms (mapq_reference): EQUAL to the reference integer wherever that is decidable, between
+    the truncated ends of the interval elsewhere; the oracle's own integer is held the same way.  Returns counts: candidates compared, those whose raw value
+    lies in [0.5, 60), the undecidable ones, and those of them where the product differs from the oracle."""
+    m = mapq_reference(ref.mapq_terms, eta=eta, screen=screen)
+    s = m["set"].copy()
+    s[ref.split_idx[ref.split_idx >= 0]] = False   # a read's split alignment: CheckSplitReads wrote its MAPQ afterwards, a difference of integer scores (split.go:103-135): exact, below
+    got, want = np.asarray(mapq).astype(np.int64), ref.mapq.astype(np.int64)
+    assert got.shape == want.shape, ("mapq", got.shape, want.shape)
+    for name, v in (("the oracle's", want), ("mapq", got)):
+        bad = np.nonzero(s & ((v < m["lo"]) | (v > m["hi"])))[0]
+        if len(bad):
+            raise AssertionError("%s differs from the high-precision reference at %s (got %s, reference %s..%s, oracle %s, terms %s)"
+                                 % (name, bad[:5], v[bad[:5]], m["lo"][bad[:5]], m["hi"][bad[:5]], want[bad[:5]], ref.mapq_terms[bad[:3]]))
+    rest = np.nonzero(~s & (got != want))[0]   # (candidates that estimateMapQualities never saw keep their initial 0)
+    assert not len(rest), ("mapq of a candidate outside the filtered lists", rest[:5], got[rest[:5]], want[rest[:5]])
+    t = ref.mapq_terms
+    mid = s & (t[:, 6] >= 0.5) & (t[:, 6] < 60)
+    und = s & ~m["decidable"]
+    m["margin"][~s] = np.inf
+    return dict(compared=int(s.sum()), in_range=int(mid.sum()), undecidable=int(und.sum()), undecidable_in_range=int((und & mid).sum()),
+                differ_undecidable=int((und & (got != want)).sum()), min_margin=float(m["margin"].min()) if s.any() else float("inf"))
+
+
 def assert_same_result(r, ref, inference=True, mapq_tol=1, rel=1e-9):
-    """bit-exact for integer/index fields; MAPQ within +-1; float scores within 1e-9 relative (BASELINE.json north_star)"""
+    """bit-exact for integer/index fields; float scores within 1e-9 relative (BASELINE.json north_star); MAPQ: against an oracle result (one that carries
+    the terms of its MAPQs, oracle_py) EXACT wherever the integer is decidable at double-precision rounding noise and inside the interval's truncated ends
+    elsewhere (assert_mapq) — and within mapq_tol of the reference's in any case; a reference without terms (a second run of the product): within mapq_tol"""
     for f in INT_FIELDS + (INF_FIELDS if inference else []):
         a, b = getattr(r, f), getattr(ref, f)
         assert a.shape == b.shape, (f, a.shape, b.shape)
@@ -91,6 +231,139 @@ def assert_same_result(r, ref, inference=True, mapq_tol=1, rel=1e-9):
     if inference:
         d = np.abs(r.mapq.astype(np.int64) - ref.mapq.astype(np.int64))
         assert (d <= mapq_tol).all(), ("mapq", np.nonzero(d > mapq_tol)[0][:5])
+        if getattr(ref, "mapq_terms", None) is not None:
+            return assert_mapq(r.mapq, ref)
+
+
+def mapq_workload(seed=31):
+    """a batch whose MAPQs live between 0 and 60: reads with two to twenty near-equal placements.  Returns (names, contigs, batch, kinds) — kinds: one word per barcode.
+
+    The genome: two random contigs with (a) six TANDEM families of 2, 3, 5, 8, 14 and 20 copies of a 900-base unit, 300 random bases between them: a family's
+    copies lie within 50 kb, so a barcode's reads on them share ONE molecule and the molecule prior cancels — what is left are the copies' differences: each copy
+    is 0.1 - 1.2 % off the unit (substitutions, a few one-base indels), a read sees 0 ... 3 of them per mate, and the pair scores differ by 0 ... 6 and more log10
+    units; the family of 14 is nearly exact (a read on it has 14 alignments and 15 scores with the pseudo-count's); the family of 20 is nineteen exact copies and a first one with three substitutions
+    290 bases apart, where most of its reads come from: a pair that covers one of them has one placement without mismatch and nineteen equal ones two log10
+    units below (9.1 with the 15 largest scores summed, 8.8 with 16), more scores than are summed, and the sixteenth would move the integer;
+    (b) three DISPERSED families of 4 copies of 3 kb, 70 kb and more apart at 0.2 - 0.8 %: a barcode's reads on one copy form a molecule, the other copies
+    candidate molecules that the optimizer may move reads to — sum_move_probability_change is finite and the molecule term binds.
+    The barcodes: `tandem` (12 pairs in one tandem family, some hanging over a unit's end into the spacer: clipped on every copy but their own, half-unit score
+    differences), `dispersed` (9 pairs on one copy of a dispersed family and 3 on another), `thin` (2 pairs on a tandem family and 2 on a dispersed one: no
+    molecule of more than four reads, none active), and of each a few that fail worthRunningRFA (`*_norfa`).  A fifth of the pairs carry three substitutions in
+    read 2: where read 1 has two equal placements, the inactive one's score without a mate (improper, -4) beats every pair score (-6): 10^score > total, NaN.
+    The centromere table covers the first tandem family (and nothing else)."""
+    rng = np.random.default_rng(seed)
+    comp = np.array([3, 2, 1, 0, 4], dtype=np.uint8)
+    contigs = [rng.choice(4, size=n, p=[0.295, 0.205, 0.205, 0.295]).astype(np.uint8) for n in (420000, 300000)]
+
+    def mutated(unit, rate, indels):
+        c = unit.copy()
+        m = rng.random(len(c)) < rate
+        c[m] = (c[m] + rng.integers(1, 4, size=int(m.sum()))) & 3
+        for _ in range(indels):
+            at = int(rng.integers(100, len(c) - 100))
+            c = np.concatenate([c[:at], c[at + 1:], rng.integers(0, 4, size=1).astype(np.uint8)]) if rng.random() < 0.5 else np.concatenate([c[:at], rng.integers(0, 4, size=1).astype(np.uint8), c[at:-1]])
+        return c
+
+    tandem, at = [], 20000   # per family: [(contig, position of copy)]
+    for n_copies in (2, 3, 5, 8, 14, 20):
+        unit = rng.integers(0, 4, size=900).astype(np.uint8)
+        copies = []
+        for k in range(n_copies):
+            rate = rng.uniform(0.0, 0.0015) if n_copies == 14 else rng.uniform(0.001, 0.012)
+            contigs[0][at:at + 900] = mutated(unit, rate, int(rng.random() < 0.25) if n_copies < 14 else 0)
+            if n_copies == 20:
+                contigs[0][at:at + 900] = unit
+                if k == 0:
+                    own = np.array([100, 390, 680])
+                    contigs[0][at + own] = (unit[own] + 1) & 3
+            copies.append((0, at))
+            at += 1200
+        tandem.append(copies)
+        at += 60000
+    cen_start, cen_end = np.array([tandem[0][0][1] - 500, -1], dtype=np.int64), np.array([tandem[0][-1][1] + 1400, -1], dtype=np.int64)
+    dispersed = []
+    for f in range(3):
+        unit = rng.integers(0, 4, size=3000).astype(np.uint8)
+        copies = []
+        for k in range(4):
+            pos = 10000 + 72000 * k + 4000 * f
+            contigs[1][pos:pos + 3000] = mutated(unit, rng.uniform(0.002, 0.008), int(rng.random() < 0.5))
+            copies.append((1, pos))
+        dispersed.append(copies)
+
+    reads, names, bc_off, kinds, do_rfa = [], [], [0], [], []
+
+    def pair(ctg, lo, hi, tag, overhang=False):
+        """an FR pair inside contigs[ctg][lo:hi) (or with read 1 starting up to 14 bases before lo)"""
+        ins = int(rng.integers(300, 520))
+        s = lo - int(rng.integers(3, 15)) if overhang else int(rng.integers(lo, hi - ins))
+        g = contigs[ctg]
+        r1, r2 = g[s:s + 143].copy(), comp[g[s + ins - 150:s + ins][::-1]]
+        for r in (r1, r2):
+            for _ in range(int(rng.choice([0, 0, 0, 1, 1, 2]))):
+                k = int(rng.integers(8, len(r) - 8)); r[k] = (r[k] + int(rng.integers(1, 4))) & 3
+        if rng.random() < 0.2:
+            for k in rng.choice(np.arange(20, 130), size=3, replace=False):
+                r2[k] = (r2[k] + 1) & 3
+        if rng.random() < 0.5:
+            r1, r2 = r2, r1
+        reads.extend([r1, r2])
+        names.append("mq:%d:%s:%d" % (seed, tag, len(names)))
+
+    def barcode(kind, rfa=1):
+        bc_off.append(len(names)); kinds.append(kind if rfa else kind + "_norfa"); do_rfa.append(rfa)
+
+    for rep in range(3):
+        for f, copies in enumerate(tandem):
+            for i in range(12):
+                c, pos = copies[0 if len(copies) == 20 and i % 3 else int(rng.integers(len(copies)))]
+                pair(c, pos, pos + 900, "t%d" % f, overhang=i % 4 == 3)
+            barcode("tandem", rfa=0 if rep == 2 and f % 2 else 1)
+    for rep in range(4):
+        for f, copies in enumerate(dispersed):
+            a, b = rng.choice(4, size=2, replace=False)
+            for i in range(12):
+                c, pos = copies[int(a if i < 9 else b)]
+                pair(c, pos, pos + 3000, "d%d" % f)
+            barcode("dispersed", rfa=0 if rep == 3 and f == 0 else 1)
+    for rep in range(8):
+        for i in range(2):
+            copies = tandem[int(rng.integers(len(tandem)))]
+            c, pos = copies[int(rng.integers(len(copies)))]
+            pair(c, pos, pos + 900, "lt")
+        for i in range(2):
+            copies = dispersed[int(rng.integers(3))]
+            c, pos = copies[int(rng.integers(4))]
+            pair(c, pos, pos + 3000, "ld")
+        barcode("thin", rfa=0 if rep == 7 else 1)
+    from lariat_amd import synth
+    lens = np.array([len(x) for x in reads], dtype=np.int64)
+    batch = capi.Batch.from_arrays(np.concatenate(reads), np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.array(bc_off, dtype=np.int32), synth._name_seeds(names),
+                                   bc_do_rfa=np.array(do_rfa, dtype=np.uint8), cen_start=cen_start, cen_end=cen_end)
+    return ["chrT", "chrD"], contigs, batch, kinds
+
+
+def mapq_coverage(ref, eta=MAPQ_ETA):
+    """which edges of the MAPQ computation a batch reaches, counted on the ORACLE's terms alone (mapq_reference of ref.mapq_terms): decidable candidates per
+    bin of the raw value, with a fractional part of a half and more, within 1e-5 below an integer, with the molecule term / the pair term the smaller one,
+    of reads with fewer than 15, exactly 15 and more than 15 scores, NaN, zeroed by a centromere"""
+    t = ref.mapq_terms
+    m = mapq_reference(t, eta=eta)
+    d = m["decidable"]
+    raw, sc, tot, sm, cen, ns = t[:, 6], t[:, 1], t[:, 2], t[:, 4], t[:, 5] != 0, t[:, 7]
+    with np.errstate(all="ignore"):
+        pair_term, mol_term = -10.0 * np.log10(1.0 - 10.0 ** sc / tot), -10.0 * np.log10(1.0 - 1.0 / sm)
+    live = d & ~cen & (raw >= 0.5) & (raw < 60)
+    cov = {"bin_0.5_1": int((live & (raw < 1)).sum()), "bin_1_10": int((live & (raw >= 1) & (raw < 10)).sum())}
+    for lo in range(10, 60, 10):
+        cov["bin_%d_%d" % (lo, lo + 10)] = int((live & (raw >= lo) & (raw < lo + 10)).sum())
+    frac = raw - np.floor(raw)
+    cov.update(frac_ge_half=int((live & (frac >= 0.5)).sum()), just_below_integer=int((live & (frac > 1 - 1e-5)).sum()),
+               molecule_term_smaller=int((live & (mol_term < pair_term)).sum()), pair_term_smaller=int((live & (pair_term < mol_term)).sum()),
+               scores_under_15=int((live & (ns < 15)).sum()), scores_15=int((live & (ns == 15)).sum()), scores_over_15=int((live & (ns > 15)).sum()),
+               nan=int((m["set"] & np.isnan(raw)).sum()), centromere_zero=int((m["set"] & cen).sum()), in_range=int((m["set"] & (raw >= 0.5) & (raw < 60)).sum()),
+               undecidable_in_range=int((m["set"] & ~d & (raw >= 0.5) & (raw < 60)).sum()), compared=int(m["set"].sum()))
+    return cov
 
 
 def exact_repeat_genome(copies=20, unit=900, spacer=400, seed=3):

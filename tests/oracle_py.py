@@ -19,6 +19,9 @@ def build():
     subprocess.check_call(["make", "-s", "-C", ORACLE_DIR])
 
 
+MAPQ_TERMS = ("set", "score", "total", "n_terms", "sum_move", "centromere", "raw", "n_scores")   # the columns of Result.mapq_terms
+
+
 class Oracle:
     def __init__(self, lib):
         self.L = L = lib
@@ -165,6 +168,11 @@ class OracleIndex:
         if self.o.L.lo_result_mapq_data(res, C.byref(mi), C.byref(mc)) == 0 and out.n_cand:
             out.md_int = np.ctypeslib.as_array(mi, shape=(out.n_cand, 7)).copy()
             out.md_sb_conf = np.ctypeslib.as_array(mc, shape=(out.n_cand,)).copy()
+        # the terms of every MAPQ (lo_result_mapq_terms): helpers.assert_same_result holds the product's MAPQ to them
+        mt = C.POINTER(C.c_double)()
+        self.o.L.lo_result_mapq_terms.argtypes = [C.POINTER(capi.LhResult), C.POINTER(C.POINTER(C.c_double))]
+        if opts.run_inference and self.o.L.lo_result_mapq_terms(res, C.byref(mt)) == 0:
+            out.mapq_terms = np.ctypeslib.as_array(mt, shape=(out.n_cand, len(MAPQ_TERMS))).copy() if out.n_cand else np.zeros((0, len(MAPQ_TERMS)))
         self.o.L.lo_result_free(res)
         return out
 

@@ -56,8 +56,10 @@ def _worker(rank, world, port, out, prefer_gpu):
         oidx = o.index_from_arrays(idx.export(), pac)
         full = oidx.align_barcodes(capi.Batch.from_arrays(r["seq"], r["seq_off"], r["bc_pair_off"], r["name_seed"]), threads=4)
         ok = all(sum((g[f] for g in gathered), []) == getattr(full, f).tolist() for f in FIELDS if f != "mapq")
-        dm = np.abs(np.array(sum((g["mapq"] for g in gathered), [])) - full.mapq)
-        ok = ok and bool((dm <= 1).all())
+        try:   # the shards' MAPQs against the oracle's terms: exact wherever the integer is decidable (helpers.assert_mapq)
+            helpers.assert_mapq(np.array(sum((g["mapq"] for g in gathered), []), dtype=np.int64), full)
+        except AssertionError:
+            ok = False
         with open(out, "w") as fh:
             fh.write("%d|%s|%s|%s|%s\n" % (int(ok), tmax, [g["range"] for g in gathered], [g["n_batches"] for g in gathered], gathered[0]["kind"]))
     dist.barrier()
