@@ -30,14 +30,16 @@
 extern "C" {
 #endif
 
-#define LH_ABI_VERSION 5
+#define LH_ABI_VERSION 6
 
 /* status codes */
 #define LH_OK 0
 #define LH_E_ARG 1       /* bad argument */
 #define LH_E_IO 2        /* index files unreadable / inconsistent (reference: gobwa.go:132-135 only logs) */
 #define LH_E_HIP 3       /* HIP runtime error (message in lh_last_error) */
-#define LH_E_CAPACITY 4  /* a per-BATCH workspace pool overflowed: split the batch and retry */
+#define LH_E_CAPACITY 4  /* a per-BATCH workspace does not fit: more pairs than the context's capacity, candidates or long-interval reads beyond a pool's bound (split the
+                          * batch and retry).  The seeds' workspace is not among them: a batch that outgrows it is aligned in rounds of whole barcodes inside
+                          * lh_align_resident (lh_last_rounds); for seeds the code means ONE BARCODE ALONE does not fit — lh_last_error names it, splitting cannot help */
 #define LH_E_NODEVICE 5  /* no HIP device / extension not usable: there is NO CPU fallback */
 #define LH_E_LIMIT 6     /* input outside documented limits (read length > LH_MAX_READ_LEN, a per-READ / per-candidate slot limit ...):
                           * splitting the batch does not help; lh_last_error names the first offending read */
@@ -109,7 +111,9 @@ typedef struct lh_context_opts {
                                * The slabs are allocated when a batch first lists a barcode for the tier, as many as the list is long (at most rfa_tier_grid;
                                * together at most 32 KiB per read of the context's capacity); tests force the tiers with small values */
     int32_t rfa_tier_grid[2]; /* at most this many slabs (= waves) per tier (1024, 64) */
-    int32_t reserved;
+    int32_t seed_budget_kb;   /* (ABI 6) what the seed, chain and region pools may take, in KiB.  0: the HBM that is free, less 2 GB, plus what the pools hold already.
+                               * Above 0 the pools never exceed it, first allocation included.  A batch whose seeds need more is aligned in rounds of whole
+                               * barcodes inside lh_align_resident, same result; tests force that with a small value.  With lanes > 1: per lane */
 } lh_context_opts;
 void lh_context_opts_init(lh_context_opts* co);
 
@@ -322,7 +326,25 @@ void lh_host_free(void* p);
 int lh_result_download(lh_context* ctx, lh_result** out);
 void lh_result_free(lh_result* r);
 
-/* per-kernel timing of the last lh_align_resident (HIP events on the context's stream), ms; names are static strings */
+/* (ABI 6) how the last lh_align_resident ran on lane `lane` (0 .. lanes - 1) of the context: whole, or — its seeds' workspace above the seed budget — in rounds.
+ * The reference never turns a work unit away (BWA's vectors grow; DoRFAForOneBarcode runs for every barcode the reader hands it, lariat.go:461-547): barcodes are
+ * independent, so the batch is cut at barcode boundaries into parts that each fit, every part runs the whole kernel sequence, and the parts' results are merged
+ * into the one lh_result the download hands out (once).  The arrays belong to the context and hold until its next lh_align_resident; barcode indices are the batch's.
+ * Ask before the next upload / select: for a batch that ran whole the largest barcode is read from the device in this call. */
+typedef struct lh_round_info {
+    int32_t n_rounds;                /* 1: the batch (the lane's part) ran whole; 0: the lane took no part in the batch */
+    int32_t max_barcode;             /* the barcode with the most seeds */
+    const int32_t* first_barcode;    /* [n_rounds + 1] the first barcode of every round, then the end */
+    const int64_t* round_seeds;      /* [n_rounds] */
+    const int64_t* round_need_bytes; /* [n_rounds] the workspace of each round's seeds */
+    int64_t need_bytes;              /* ... of the whole batch's */
+    int64_t budget_bytes;            /* what the workspace may take (lh_context_opts.seed_budget_kb) */
+    int64_t max_barcode_need_bytes;  /* above the budget: LH_E_CAPACITY, the one barcode cannot be split */
+} lh_round_info;
+int lh_last_rounds(lh_context* ctx, int32_t lane, lh_round_info* out);
+
+/* per-kernel timing of the last lh_align_resident (HIP events on the context's stream), ms; names are static strings.  After a run in rounds: per-kernel sums over the
+ * rounds, plus "k1_discarded" (the K1 pass over the whole batch that found the overflow), "k_round_plan" and "k_batch_view" */
 int lh_last_timings(lh_context* ctx, int32_t* n, const char* const** names, const float** ms);
 
 /* stage dump of the candidate-generation front end (mem_align1_core) for the resident batch: parity tests only */

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LARIAT_HIP_LIB") or os.path.join(_HERE, "_build", "liblariat_hip.so")
 
 LH_OK = 0
-LH_ABI_VERSION = 5
+LH_ABI_VERSION = 6
 LH_E_ARG, LH_E_IO, LH_E_HIP, LH_E_CAPACITY, LH_E_NODEVICE, LH_E_LIMIT = 1, 2, 3, 4, 5, 6
 # lh_opts.flags
 LH_REC_DEBUG_TAGS = 1
@@ -54,7 +54,12 @@ class LhIndexOpts(C.Structure):
 
 class LhContextOpts(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("smem_grid", C.c_int32), ("aln_grid", C.c_int32), ("rfa_grid", C.c_int32), ("rfa_slab_kb", C.c_int32),
-                ("lanes", C.c_int32), ("big_slots", C.c_int32), ("rfa_tier_kb", C.c_int32 * 2), ("rfa_tier_grid", C.c_int32 * 2), ("reserved", C.c_int32)]
+                ("lanes", C.c_int32), ("big_slots", C.c_int32), ("rfa_tier_kb", C.c_int32 * 2), ("rfa_tier_grid", C.c_int32 * 2), ("seed_budget_kb", C.c_int32)]
+
+
+class LhRoundInfo(C.Structure):
+    _fields_ = [("n_rounds", C.c_int32), ("max_barcode", C.c_int32), ("first_barcode", c_i32p), ("round_seeds", c_i64p), ("round_need_bytes", c_i64p),
+                ("need_bytes", C.c_int64), ("budget_bytes", C.c_int64), ("max_barcode_need_bytes", C.c_int64)]
 
 
 class LhBatch(C.Structure):
@@ -302,6 +307,7 @@ def _declare(L):
     L.lh_result_download.argtypes = [C.c_void_p, C.POINTER(C.POINTER(LhResult))]
     L.lh_result_free.argtypes = [C.POINTER(LhResult)]
     L.lh_last_timings.argtypes = [C.c_void_p, c_i32p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float))]
+    L.lh_last_rounds.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LhRoundInfo)]
     L.lh_stage_dump_resident.argtypes = [C.c_void_p, C.POINTER(LhOpts), C.POINTER(C.POINTER(LhStageDump))]
     L.lh_stage_dump_free.argtypes = [C.POINTER(LhStageDump)]
     L.lh_get_seq.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_char_p]
@@ -784,6 +790,16 @@ class Context:
         self.lib.check(self.lib.L.lh_last_timings(self.h, C.byref(n), C.byref(names), C.byref(ms)))
         return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
 
+    def rounds(self, lane=0):
+        """lh_last_rounds: how the last align_resident ran on a lane — dict(n_rounds, first_barcode, round_seeds, round_need_bytes, need_bytes, budget_bytes,
+        max_barcode, max_barcode_need_bytes); ask before the next upload"""
+        ri = LhRoundInfo()
+        self.lib.check(self.lib.L.lh_last_rounds(self.h, int(lane), C.byref(ri)))
+        n = int(ri.n_rounds)
+        return dict(n_rounds=n, first_barcode=_view(ri.first_barcode, n + 1 if n else 0, np.int32), round_seeds=_view(ri.round_seeds, n, np.int64),
+                    round_need_bytes=_view(ri.round_need_bytes, n, np.int64), need_bytes=int(ri.need_bytes), budget_bytes=int(ri.budget_bytes),
+                    max_barcode=int(ri.max_barcode), max_barcode_need_bytes=int(ri.max_barcode_need_bytes))
+
     def stage_dump(self, batch=None, opts=None):
         opts = opts or self.lib.opts()
         if batch is not None:
@@ -925,6 +941,6 @@ EXPORTED_SYMBOLS = [
     "lh_ingest_open", "lh_ingest_next", "lh_ingest_batch_free", "lh_ingest_close", "lh_name_seed",
     "lh_records_text", "lh_records_text_ex", "lh_records_free", "lh_bam_open", "lh_bam_append", "lh_bam_set_flags", "lh_bam_close",
     "lh_index_free", "lh_index_build", "lh_context_create", "lh_context_free", "lh_align_barcodes", "lh_batch_upload", "lh_align_resident",
-    "lh_result_download", "lh_result_free", "lh_last_timings", "lh_stage_dump_resident", "lh_stage_dump_free", "lh_get_seq", "lh_device_memory", "lh_diag_gosort", "lh_diag_gosort_split", "lh_diag_bitonic", "lh_diag_introsort", "lh_diag_random_read", "lh_diag_valu_rate", "lh_diag_rescue_sw", "lh_diag_go_rand", "lh_diag_rescue_dedup",
+    "lh_result_download", "lh_result_free", "lh_last_timings", "lh_last_rounds", "lh_stage_dump_resident", "lh_stage_dump_free", "lh_get_seq", "lh_device_memory", "lh_diag_gosort", "lh_diag_gosort_split", "lh_diag_bitonic", "lh_diag_introsort", "lh_diag_random_read", "lh_diag_valu_rate", "lh_diag_rescue_sw", "lh_diag_go_rand", "lh_diag_rescue_dedup",
     "lh_index_opts_init", "lh_context_opts_init", "lh_index_build_device", "lh_index_export", "lh_index_save", "lh_synth_genome", "lh_synth_reads", "lh_synth_write_fastq9", "lh_diag_index_check", "lh_batch_upload_slot", "lh_batch_select", "lh_bam_concat", "lh_reference_pack", "lh_index_set_holes", "lh_diag_index_digest", "lh_index_set_alt", "lh_index_alt", "lh_bam_set_level", "lh_bam_timings", "lh_result_download_begin", "lh_result_download_end", "lh_batch_stage_slot", "lh_host_alloc", "lh_host_free",
 ]

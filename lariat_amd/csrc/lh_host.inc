@@ -24,6 +24,7 @@
 #include "k_chain_cl.h"
 #include "k_rfa.h"   // pulls in k_seed/k_chain/k_extend/k_global/k_dedup/k_rescue/k_aln
 #include "k_rescue3.h"
+#include "k_rounds.h"
 #include "lh_result_cols.h"
 
 static void lh_print_wd(const int32_t* d_wd) {   // (LH_DEBUG_SYNC builds of a run: the pipeline's watchdog slots after every launch)
@@ -84,10 +85,10 @@ struct lh_context {
     i64 cap_pairs = 0, cap_reads = 0, cap_bases = 0, pool_cap = 0, regpool_cap = 0, cap_bc = 0;
     // device memory by lifetime (lh_workspace.h).  mem: the whole context's; seed_mem follows a batch's seed total (pool_cap, regpool_cap: alloc_seed_pools), cand_mem its
     // candidate total (cand_cap: alloc_cand_pools); regrown on their own: K1's big slab and list (big_cap), K6's job arrays (rjob_cap), the download's pack buffers
-    // (pack_cap), each K8 tier's slabs (grid_rfa_mid[k]).  A batch slot's arrays: DevBatch::mem
-    DevGroup mem, seed_mem, cand_mem, big_mem, rjob_mem, pack_mem, tier_mem[2];
+    // (pack_cap), each K8 tier's slabs (grid_rfa_mid[k]), the rounds' plan array and batch view (rb).  A batch slot's arrays: DevBatch::mem
+    DevGroup mem, seed_mem, cand_mem, big_mem, rjob_mem, pack_mem, tier_mem[2], round_mem;
     void free_device() {   // everything this context owns on the device
-        for (DevGroup* g : {&mem, &seed_mem, &cand_mem, &big_mem, &rjob_mem, &pack_mem, &tier_mem[0], &tier_mem[1]}) g->release();
+        for (DevGroup* g : {&mem, &seed_mem, &cand_mem, &big_mem, &rjob_mem, &pack_mem, &tier_mem[0], &tier_mem[1], &round_mem}) g->release();
         for (DevBatch& sl : slots) sl.mem.release();
         for (void* q : free_later) hipFree(q);
         free_later.clear();
@@ -127,6 +128,7 @@ struct lh_context {
     i64 *d_cigar_off = nullptr, *d_mm_off = nullptr; uint32_t *d_pack_a = nullptr, *d_pack_b = nullptr, *d_pack_c = nullptr; i64 pack_cap = 0;   // the download's scans and packed arrays
     std::shared_ptr<PinPool> pin_pool = std::make_shared<PinPool>();
     bool dump_stop_after_dedup = false; bool ran_inference = false;
+    bool in_round = false;   // the selection is a part of the resident batch (align_rounds)
     // K8 (k_rfa.h)
     DInf S; uint8_t* d_slab = nullptr; i64 slab_bytes = 0; int grid_rfa = 0; RfaCounters* d_bc_next = nullptr;
     uint8_t* d_slab2 = nullptr; i64 slab2_bytes = 0; int grid_rfa2 = 0;
@@ -152,6 +154,9 @@ struct lh_context {
     std::deque<DevBatch> slots; std::mutex slot_mu;   // slot_mu: slots' size and `filled`, sel_slot / resident, free_later.  (A deque: growing it does not move the slots another thread holds)
     std::vector<void*> free_later;   // device buffers a staging thread replaced: freed by the aligning thread
     lh_context_opts co;   // launch geometry (defaults filled in)
+    // rounds (k_rounds.h, align_rounds): a batch whose seed workspace exceeds the budget is aligned part by part inside one lh_align_resident
+    RoundBufs rb; RoundPlanBlock plan; RoundState rounds;
+    lh_result* round_result = nullptr;   // the parts' results merged: handed out by the next download
     uint32_t flags = 0;   // lh_opts.flags of the running call
     // lanes > 1 (lh_lanes.inc): further, smaller pipelines owned by this one; a batch is cut at barcode boundaries and the parts
     // run side by side from as many host threads
@@ -220,6 +225,27 @@ static int rfa_alloc(lh_context* c);
 static int rfa_run(lh_context* c, const DOpts& o, int& t);
 static int stage2_alloc(lh_context* c);
 static int stage2_run(lh_context* c, const DOpts& o, int& t);
+#define LH_NEED_ROUNDS (-1)   // run_front, internal: the batch's seed workspace exceeds its budget (pipe_align then aligns it in rounds)
+
+// ---- the seed budget.  The seed, chain and region pools follow a batch's seed total; what they may take is the budget: lh_context_opts.seed_budget_kb, or (0) the
+// HBM that is free plus what the pools hold already, less 2 GB for the other buffers that follow a batch.  A batch that needs more is aligned in rounds (align_rounds).
+// bytes per entry of the seed pools plus one of the region pools (alloc_seed_pools' arrays; a low-complexity read has up to max_occ seeds per interval: ~0.5 KB each)
+static const i64 LH_REG_ENTRY_BYTES = (i64)(2 * sizeof(DReg) + 12);                                                               // per entry of the region pools
+static const i64 LH_SEED_ENTRY_BYTES = (i64)(sizeof(DSeed) * 2 + 4 * 4 + sizeof(DChainTmp) + sizeof(DChain) + 16 + 40);            // per entry of the seed pools
+static const i64 LH_SEED_POOL_BYTES = LH_SEED_ENTRY_BYTES + LH_REG_ENTRY_BYTES;   // per seed: one of each (the need counts a rescue slot as much: room for the buffers that grow later)
+static i64 seed_fixed_slots(const lh_context* c) { return c->cap_reads * LH_RESCUE_SLOTS; }
+static i64 seed_need(const lh_context* c, i64 seeds) { return lh_seed_need(seeds, seed_fixed_slots(c), LH_SEED_POOL_BYTES); }
+static int seed_budget(const lh_context* c, i64* budget) {
+    if (c->co.seed_budget_kb > 0) { *budget = (i64)c->co.seed_budget_kb << 10; return LH_OK; }
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    *budget = (i64)free_b + c->pool_cap * LH_SEED_ENTRY_BYTES + c->regpool_cap * LH_REG_ENTRY_BYTES - 2000000000;   // (what the pools hold is theirs to use again)
+    return LH_OK;
+}
+// the largest pool_cap a fixed budget allows (no fixed budget: no bound)
+static i64 pool_cap_limit(const lh_context* c) {
+    return c->co.seed_budget_kb > 0 ? ((i64)c->co.seed_budget_kb << 10) / LH_SEED_POOL_BYTES - seed_fixed_slots(c) : INT64_MAX;
+}
 
 // pools whose size follows the number of seeds of a batch (pool_cap) or of regions (regpool_cap = seeds + rescue slots)
 static int alloc_seed_pools(lh_context* c, i64 pool_cap) {
@@ -237,7 +263,10 @@ static int alloc_seed_pools(lh_context* c, i64 pool_cap) {
 }
 static int alloc_cand_pools(lh_context* c, i64 cand_cap);
 // the two pools' sizes in a new context; both grow on demand (run_front, stage2_run: a batch's totals are known before anything is written there)
-static i64 first_pool_cap(const lh_context* c) { return c->cap_reads * 16 > LH_POOL_FLOOR ? c->cap_reads * 16 : LH_POOL_FLOOR; }   // ~10 seeds per 150-base read at hg38 scale
+static i64 first_pool_cap(const lh_context* c) {   // ~10 seeds per 150-base read at hg38 scale; within a fixed seed budget from the first allocation on
+    const i64 want = c->cap_reads * 16 > LH_POOL_FLOOR ? c->cap_reads * 16 : LH_POOL_FLOOR, most = pool_cap_limit(c);
+    return want < most ? want : most;
+}
 static i64 first_cand_cap(const lh_context* c) { return c->cap_reads * 3 > LH_POOL_FLOOR ? c->cap_reads * 3 : LH_POOL_FLOOR; }     // ~1.1 candidates/read on unique sequence
 
 static void pipe_free(lh_context* c);
@@ -296,6 +325,9 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
         DALLOC(g, c->d_next_read, 1);
     }
     DALLOC(g, c->d_seed_off, N + 1); DALLOC(g, c->d_n_chains, N);
+    if (c->co.seed_budget_kb < 0 || pool_cap_limit(c) < 1)
+        return set_err(LH_E_ARG, "lh_context_opts.seed_budget_kb = " + std::to_string(c->co.seed_budget_kb) + ": the rescue slots of " + std::to_string(max_pairs) +
+                                     " pairs alone take " + std::to_string((seed_need(c, 0) >> 10) + 1) + " KiB");
     { int rc = alloc_seed_pools(c, first_pool_cap(c)); if (rc) return rc; }
     DALLOC(g, c->d_ctr, LH_CTR_SLOTS);
     DALLOC(g, c->d_wd, LH_WD_SLOTS);
@@ -315,6 +347,8 @@ static void pipe_free(lh_context* c) {
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->dl_pending) { lh_result* r = nullptr; if (c->dl_finish && c->dl_finish(&r) == LH_OK) lh_result_free(r); c->dl_pending = false; }
     if (c->h_peek) hipHostFree(c->h_peek);
+    if (c->plan.p) hipHostFree(c->plan.p);
+    if (c->round_result) lh_result_free(c->round_result);
     if (c->dl_stream) hipStreamDestroy(c->dl_stream);
     if (c->up_stream) hipStreamDestroy(c->up_stream);
     if (c->ev_pack) hipEventDestroy(c->ev_pack);
@@ -561,19 +595,23 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         }
         c->big_base = 0;
         const i64 total = c->h_peek->k1.seeds;
-        if (total > c->pool_cap) {
-            // the pools follow the batch as far as HBM allows (a batch of low-complexity reads has up to max_occ seeds per interval: ~0.5 KB
-            // of workspace per seed); what does not fit is a capacity error with its size, never a per-read refusal
-            c->seed_mem.release(); c->pool_cap = c->regpool_cap = 0;
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(hipMemGetInfo(&free_b, &total_b));
-            const double per_seed = sizeof(DSeed) * 2 + 4 * 4 + sizeof(DChainTmp) + sizeof(DChain) + 16 + 2.0 * sizeof(DReg) + 12 + 40;
-            const double need = ((double)total * 1.25 + (double)c->cap_reads * LH_RESCUE_SLOTS) * per_seed;
-            if (need > (double)free_b - 2e9)
-                return set_err(LH_E_CAPACITY, "the batch has " + std::to_string(total) + " seeds: their workspace (" + std::to_string((long long)(need / 1e9)) + " GB) does not fit the " +
-                                                  std::to_string((long long)(free_b / 1000000000)) + " GB of HBM that are free: split the batch");
-            int rc = alloc_seed_pools(c, total + total / 4);
-            if (rc) return rc;
+        if (!c->in_round) c->rounds.total_seeds = total;
+        if (total > c->pool_cap || c->co.seed_budget_kb > 0) {
+            // the pools follow the batch as far as their budget allows.  What does not fit is aligned in rounds of whole barcodes (align_rounds: this pass is discarded);
+            // a stage dump shows one pass over the whole batch, so there it stays a capacity error with its size, never a per-read refusal
+            const i64 need = seed_need(c, total);
+            i64 budget = 0;
+            { int rc = seed_budget(c, &budget); if (rc) return rc; }
+            if (!c->in_round) c->rounds.budget = budget;
+            if (need > budget) {
+                if (!c->dump_stop_after_dedup && !c->in_round) return LH_NEED_ROUNDS;
+                return set_err(LH_E_CAPACITY, "the batch has " + std::to_string(total) + " seeds: their workspace (" + std::to_string((long long)(need / 1000000000)) + " GB) does not fit the " +
+                                                  std::to_string((long long)(budget / 1000000000)) + " GB of its budget (seed_budget_kb, or the HBM that is free): split the batch");
+            }
+            if (total > c->pool_cap) {
+                int rc = alloc_seed_pools(c, total + total / 4);
+                if (rc) return rc;
+            }
         }
     }
     T_BEGIN("k_seed");
@@ -631,6 +669,160 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
     return LH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ rounds
+// the plan's prefix array for n_bc barcodes and, with view, the buffers of a part as a batch of its own (at most the whole batch); the plan block for as many cuts
+static int round_mem_for(lh_context* c, int n_bc, bool view, i64 n_reads, i64 n_bases) {
+    RoundBufs& rb = c->rb;
+    if (n_bc > rb.cap_bc || (view && (n_reads > rb.cap_reads || n_bases > rb.cap_bases))) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->round_mem.release();
+        const bool v = view || rb.cap_reads > 0;
+        const i64 cb = n_bc > rb.cap_bc ? n_bc : rb.cap_bc, cr = !v ? 0 : n_reads > rb.cap_reads ? n_reads : rb.cap_reads, cs = !v ? 0 : n_bases > rb.cap_bases ? n_bases : rb.cap_bases;
+        rb = RoundBufs();
+        DevGroup& g = c->round_mem;
+        DALLOC(g, rb.prefix, cb + 1);
+        if (v) { DALLOC(g, rb.v_bc_pair_off, cb + 1); DALLOC(g, rb.v_seq_off, cr + 1); DALLOC(g, rb.v_seq, cs / 8 + 8); }
+        rb.cap_bc = cb; rb.cap_reads = cr; rb.cap_bases = cs;
+    }
+    if (n_bc > c->plan.cap_rounds) {
+        if (c->plan.p) { HIPCHK(hipStreamSynchronize(c->stream)); hipHostFree(c->plan.p); }
+        c->plan = RoundPlanBlock();
+        HIPCHK(hipHostMalloc((void**)&c->plan.p, RoundPlanBlock::bytes(n_bc), hipHostMallocDefault));
+        c->plan.cap_rounds = n_bc;
+    }
+    return LH_OK;
+}
+// the selected batch's seeds (d_seed_off: k_scan_seeds has run) cut into parts within `budget`: the plan in c->plan once the stream is synchronised
+static int round_plan(lh_context* c, i64 budget, bool view) {
+    { int rc = round_mem_for(c, c->n_bc, view, c->n_reads, c->n_bases); if (rc) return rc; }
+    LH_LAUNCH(k_round_cost, (c->n_bc + 256) / 256, 256, c->stream, c->n_bc, (const int32_t*)c->d_bc_pair_off, (const i64*)c->d_seed_off, c->rb.prefix);
+    LH_LAUNCH(k_round_plan, 1, 64, c->stream, c->n_bc, (const i64*)c->rb.prefix, (const int32_t*)c->d_bc_pair_off, (const i64*)c->d_seq_off, budget, seed_fixed_slots(c),
+              LH_SEED_POOL_BYTES, (int)c->plan.cap_rounds, c->plan.hdr(), c->plan.cut_bc(), c->plan.cut_pair(), c->plan.cut_base(), c->plan.part_seeds(), c->d_wd);
+    return LH_OK;
+}
+
+static int merge_results(lh_result* a, lh_result* b, lh_result** out);   // (lh_lanes.inc)
+static int pipe_download(lh_context* c, lh_result** out);                // (lh_host_stage2.inc)
+struct TimeSums {   // per-kernel times summed over the rounds, in the order of their first appearance
+    const char* names[LH_NSTAGE]; float ms[LH_NSTAGE]; int n = 0;
+    void add(const char* name, float v) {
+        int i = 0;
+        while (i < n && strcmp(names[i], name)) ++i;
+        if (i == n) { if (n == LH_NSTAGE) return; names[n] = name; ms[n] = 0; ++n; }
+        ms[i] += v;
+    }
+};
+// the times of the t entries just run (the stream is synchronised)
+static int add_times(lh_context* c, int t, TimeSums& sums, const char* as_one) {
+    for (int i = 0; i < t; ++i) {
+        float v = 0;
+        HIPCHK(hipEventElapsedTime(&v, c->ev[i], c->ev[i + 1]));
+        sums.add(as_one ? as_one : c->tnames[i], v);
+    }
+    return LH_OK;
+}
+
+// The selected batch does not fit its seed budget as a whole: align it part by part.  The K1 pass that found out is discarded (re-running K1 per part costs that one
+// pass in the overflow case and nothing otherwise); every part is a batch view (k_batch_view) that runs the unchanged kernel sequence and downloads, and the parts'
+// results are merged column by column as the lanes' are (merge_results) before the next part's kernels reuse the result arrays.  t: the discarded pass's entries.
+static int align_rounds(lh_context* c, const DOpts& o, int t) {
+    TimeSums sums;
+    HIPCHK(hipEventRecord(c->ev[t], c->stream));
+    const i64 total = c->rounds.total_seeds;
+    // the view's buffers take HBM too: with the budget read from the free memory, plan after they exist
+    { int rc = round_mem_for(c, c->n_bc, true, c->n_reads, c->n_bases); if (rc) return rc; }
+    i64 budget = 0;
+    { int rc = seed_budget(c, &budget); if (rc) return rc; }
+    HIPCHK(hipEventRecord(c->ev[LH_NSTAGE - 1], c->stream));
+    { int rc = round_plan(c, budget, true); if (rc) return rc; }
+    HIPCHK(hipEventRecord(c->ev[LH_NSTAGE], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { int rc = add_times(c, t, sums, "k1_discarded"); if (rc) return rc; }
+    { float v = 0; HIPCHK(hipEventElapsedTime(&v, c->ev[LH_NSTAGE - 1], c->ev[LH_NSTAGE])); sums.add("k_round_plan", v); }
+    const RoundPlanBlock& P = c->plan;
+    RoundState& R = c->rounds;
+    R.budget = budget; R.have_max = true; R.max_bc = P.hdr()->max_barcode; R.max_bc_seeds = P.hdr()->max_barcode_seeds;
+    const i64 n_rounds = P.hdr()->n_rounds;
+    if (n_rounds == 0)
+        return set_err(LH_E_CAPACITY, "barcode " + std::to_string(R.max_bc) + " has " + std::to_string(R.max_bc_seeds) + " seeds: their workspace (" + std::to_string(seed_need(c, R.max_bc_seeds)) +
+                                          " bytes) does not fit the budget of " + std::to_string(budget) + " bytes (seed_budget_kb, or the HBM that is free), and a barcode is never split");
+    bool ok = n_rounds > 0 && n_rounds <= c->n_bc && P.hdr()->total_seeds == total && P.cut_bc()[0] == 0 && P.cut_bc()[n_rounds] == c->n_bc && P.cut_pair()[n_rounds] == c->n_pairs &&
+              P.cut_base()[n_rounds] == c->n_bases;
+    for (i64 r = 0; ok && r < n_rounds; ++r)
+        ok = P.cut_bc()[r] < P.cut_bc()[r + 1] && P.cut_pair()[r] < P.cut_pair()[r + 1] && P.cut_base()[r] <= P.cut_base()[r + 1] && seed_need(c, P.part_seeds()[r]) <= budget;
+    if (!ok) return set_err(LH_E_HIP, "the round plan is inconsistent (k_round_plan, watchdog slot " + std::to_string(LH_WD_ROUND_PLAN) + ")");
+    R.first_bc.assign(P.cut_bc(), P.cut_bc() + n_rounds + 1);
+    R.seeds.assign(P.part_seeds(), P.part_seeds() + n_rounds);
+    R.need.clear();
+    for (i64 s : R.seeds) R.need.push_back(seed_need(c, s));
+    // a download the host began for the PREVIOUS batch and has not collected: its copies must have ended before a part's download reuses the copy stream's event;
+    // it stays pending for the host while the parts' downloads come and go
+    const bool host_pending = c->dl_pending;
+    std::function<int(lh_result**)> host_finish;
+    if (host_pending) { HIPCHK(hipEventSynchronize(c->ev_dl)); host_finish = std::move(c->dl_finish); c->dl_pending = false; }
+    struct Whole {   // the batch's own selection, back in place however this ends
+        lh_context* c; uint8_t* seq; i64* seq_off; u64* name_seed; int32_t* bc_pair_off; uint8_t* bc_do_rfa; int n_pairs, n_reads, n_bc; i64 n_bases;
+        bool pending; std::function<int(lh_result**)>* finish;
+        ~Whole() {
+            c->d_seq = seq; c->d_seq_off = seq_off; c->d_name_seed = name_seed; c->d_bc_pair_off = bc_pair_off; c->d_bc_do_rfa = bc_do_rfa;
+            c->n_pairs = n_pairs; c->n_reads = n_reads; c->n_bc = n_bc; c->n_bases = n_bases; c->in_round = false;
+            if (pending) { c->dl_pending = true; c->dl_finish = std::move(*finish); }
+        }
+    } whole{c, c->d_seq, c->d_seq_off, c->d_name_seed, c->d_bc_pair_off, c->d_bc_do_rfa, c->n_pairs, c->n_reads, c->n_bc, c->n_bases, host_pending, &host_finish};
+    c->in_round = true;
+    lh_result* acc = nullptr;
+    for (i64 r = 0; r < n_rounds; ++r) {
+        const int b0 = (int)P.cut_bc()[r], b1 = (int)P.cut_bc()[r + 1], p0 = (int)P.cut_pair()[r], p1 = (int)P.cut_pair()[r + 1];
+        const i64 s0 = P.cut_base()[r], s1 = P.cut_base()[r + 1];
+        const int nb = b1 - b0, np = p1 - p0, nr = 2 * np;
+        int rt = 0;
+        HIPCHK(hipEventRecord(c->ev[LH_NSTAGE - 1], c->stream));
+        {
+            const i64 work = (s1 - s0) / 8 > nr ? (s1 - s0) / 8 : nr;
+            LH_LAUNCH(k_batch_view, (int)(work / 256 + 1 < 4096 ? work / 256 + 1 : 4096), 256, c->stream, nb, nr, s1 - s0, b0, p0, s0, (const int32_t*)whole.bc_pair_off,
+                      (const i64*)whole.seq_off, (const uint8_t*)whole.seq, c->rb.v_bc_pair_off, c->rb.v_seq_off, c->rb.v_seq);
+        }
+        HIPCHK(hipEventRecord(c->ev[LH_NSTAGE], c->stream));
+        c->d_seq = (uint8_t*)c->rb.v_seq; c->d_seq_off = c->rb.v_seq_off; c->d_bc_pair_off = c->rb.v_bc_pair_off;
+        c->d_name_seed = whole.name_seed + p0; c->d_bc_do_rfa = whole.bc_do_rfa + b0;
+        c->n_pairs = np; c->n_reads = nr; c->n_bc = nb; c->n_bases = s1 - s0;
+        int rc = run_front(c, o, rt);
+        if (!rc) rc = stage2_run(c, o, rt);
+        lh_result* part = nullptr;
+        if (!rc) {
+            hipError_t e = hipEventRecord(c->ev[rt], c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) rc = set_err(LH_E_HIP, std::string("round ") + std::to_string(r) + ": " + hipGetErrorString(e));
+        }
+        if (!rc) rc = add_times(c, rt, sums, nullptr);
+        if (!rc) { float v = 0; hipEventElapsedTime(&v, c->ev[LH_NSTAGE - 1], c->ev[LH_NSTAGE]); sums.add("k_batch_view", v); }
+        if (!rc) {
+            c->ran = true;
+            rc = pipe_download(c, &part);   // (the watchdog slots are read and cleared with every part's result)
+            c->ran = false;
+            if (rc) rc = set_err(rc, "round " + std::to_string(r) + " of " + std::to_string(n_rounds) + " (its reads start at read " + std::to_string(2 * (i64)p0) + " of the batch): " + g_err);
+        }
+        if (!rc && acc) {
+            lh_result* m = nullptr;
+            rc = merge_results(acc, part, &m);
+            lh_result_free(acc); lh_result_free(part);
+            acc = m; part = nullptr;
+        } else if (!rc) acc = part;
+        if (rc) {
+            const std::string why = g_err;
+            for (int i = 0; i < 3; ++i) hipStreamSynchronize(c->aux[i]);
+            hipStreamSynchronize(c->stream);
+            if (acc) lh_result_free(acc);
+            return set_err(rc, why);
+        }
+    }
+    c->round_result = acc;
+    R.n_rounds = (int)n_rounds;
+    c->n_t = sums.n;
+    for (int i = 0; i < sums.n; ++i) { c->tnames[i] = sums.names[i]; c->tms[i] = sums.ms[i]; }
+    return LH_OK;
+}
+
 static int pipe_align(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
     if (!c->resident) return set_err(LH_E_ARG, "no batch resident: call lh_batch_upload first");
@@ -642,6 +834,9 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
         { std::lock_guard<std::mutex> g(c->slot_mu); fl.swap(c->free_later); }
         for (void* q : fl) hipFree(q);
     }
+    if (c->round_result) { lh_result_free(c->round_result); c->round_result = nullptr; }   // (an earlier batch's, never downloaded)
+    c->rounds.clear();
+    c->ran = false;
     // a regrow that failed in an earlier call left the context without that group's buffers (capacity 0): start again with the sizes of a new context
     if (!c->pool_cap) { int rc = alloc_seed_pools(c, first_pool_cap(c)); if (rc) return rc; }
     if (!c->cand_cap) { int rc = alloc_cand_pools(c, first_cand_cap(c)); if (rc) return rc; }
@@ -650,7 +845,9 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     c->flags = opts->flags;
     int t = 0;
     int rc = run_front(c, o, t);
-    if (!rc) rc = stage2_run(c, o, t);
+    const bool in_rounds = rc == LH_NEED_ROUNDS;
+    if (in_rounds) rc = align_rounds(c, o, t);
+    else if (!rc) rc = stage2_run(c, o, t);
     if (rc) {
         // an error return may come between a fork onto the auxiliary stream (K4's wave kernels beside the rounds, K6's long-list replay) and its join: nothing
         // of this call may still be running on the context's buffers when the caller frees or reuses them
@@ -658,11 +855,14 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
         hipStreamSynchronize(c->stream);
         return rc;
     }
-    HIPCHK(hipEventRecord(c->ev[t], c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipGetLastError());
-    c->n_t = t;
-    for (int i = 0; i < t; ++i) HIPCHK(hipEventElapsedTime(&c->tms[i], c->ev[i], c->ev[i + 1]));
+    if (!in_rounds) {
+        HIPCHK(hipEventRecord(c->ev[t], c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        c->n_t = t;
+        for (int i = 0; i < t; ++i) HIPCHK(hipEventElapsedTime(&c->tms[i], c->ev[i], c->ev[i + 1]));
+        c->rounds.n_rounds = 1;
+    }
     c->ran = true;
     return LH_OK;
 }

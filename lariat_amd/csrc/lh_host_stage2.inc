@@ -410,6 +410,14 @@ static int pipe_download_begin(lh_context* c) {
     if (!c) return set_err(LH_E_ARG, "lh_result_download: null argument");
     if (!c->ran) return set_err(LH_E_ARG, "nothing to download: call lh_align_resident first");
     if (c->dl_pending) return set_err(LH_E_ARG, "lh_result_download_begin: the previous download has not been collected (lh_result_download_end)");
+    if (c->rounds.n_rounds > 1) {   // a batch aligned in rounds: every part was downloaded and merged inside lh_align_resident, nothing is left to enqueue
+        if (!c->round_result) return set_err(LH_E_ARG, "lh_result_download: the result of a batch aligned in rounds is handed out once");
+        lh_result* r = c->round_result;
+        c->round_result = nullptr;
+        c->dl_pending = true;
+        c->dl_finish = [r](lh_result** out) -> int { *out = r; return LH_OK; };
+        return LH_OK;
+    }
     HIPCHK(hipSetDevice(c->idx->device));
     const int N = c->n_reads;
     // three small read-backs first: the OR of the status words, the candidate total, the packed CIGAR / mismatch totals
@@ -613,10 +621,25 @@ static int rfa_tier_slabs(lh_context* c, int k, i64 listed, bool a_slab_each = f
     if (want < 1) want = 1;
     // (a_slab_each: the barcodes routed to the tier up front are a batch's largest — two of them in turn on one wave is the launch's duration doubled)
     if (c->d_slab_mid[k] && want <= (a_slab_each ? 1 : 2) * (i64)c->grid_rfa_mid[k]) return LH_OK;
-    if (c->d_slab_mid[k]) { HIPCHK(hipStreamSynchronize(c->stream)); c->tier_mem[k].release(); c->grid_rfa_mid[k] = 0; }
     i64 gk = want + want / 2 + 4;
     gk = gk > c->grid_rfa_mid_max[k] ? c->grid_rfa_mid_max[k] : gk;
-    DALLOC(c->tier_mem[k], c->d_slab_mid[k], (size_t)gk * (size_t)c->slab_mid_bytes[k]);
+    // The new slabs are allocated BEFORE the old ones are freed, and fewer are tried when they do not fit (this runs in the middle of a batch, and of a round): a tier
+    // that has slabs keeps them if no larger set can be had — fewer slabs only cost time — and only a tier that cannot get a single slab fails the batch
+    const i64 have = c->d_slab_mid[k] ? c->grid_rfa_mid[k] : 0;
+    uint8_t* fresh = nullptr;
+    DevGroup grown;   // the new slabs; once they are swapped in, the old ones
+    DevGroup& into = have ? grown : c->tier_mem[k];
+    uint8_t*& slot = have ? fresh : c->d_slab_mid[k];
+    for (;; gk = gk / 2 > have ? gk / 2 : have + 1) {
+        if (gk <= have) { g_err.clear(); return LH_OK; }
+        if (into.alloc(slot, (size_t)gk * (size_t)c->slab_mid_bytes[k]) == LH_OK) break;
+        if (gk <= have + 1) { if (have) { g_err.clear(); return LH_OK; } return LH_E_HIP; }   // (the message: dalloc's)
+    }
+    if (have) {
+        HIPCHK(hipStreamSynchronize(c->stream));   // (the launches that use the old slabs)
+        std::swap(c->d_slab_mid[k], fresh);        // (a buffer goes with the variable that holds it: DevGroup)
+        grown.release();
+    }
     c->grid_rfa_mid[k] = (int)gk;
     return LH_OK;
 }

@@ -121,7 +121,10 @@ int lh_batch_select(lh_context* c, int32_t slot) {
 
 int lh_align_resident(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
-    if (!lanes_split(c)) return pipe_align(c, opts);
+    if (!lanes_split(c)) {
+        for (lh_context* p : c->more) p->rounds.clear();   // (lh_last_rounds: they took no part)
+        return pipe_align(c, opts);
+    }
     const size_t M = c->more.size();
     std::vector<int> rcs(M, LH_OK);
     std::vector<std::string> errs(M);
@@ -131,6 +134,37 @@ int lh_align_resident(lh_context* c, const lh_opts* opts) {
     for (auto& t : th) t.join();
     if (rc) return rc;
     for (size_t k = 0; k < M; ++k) if (rcs[k]) return set_err(rcs[k], errs[k]);
+    return LH_OK;
+}
+
+// How a lane ran the last lh_align_resident (rounds live inside a pipeline: every lane plans its own part against its own budget).  Barcode indices are the
+// batch's.  For a part that ran whole, the barcode with the most seeds is asked of the device here (the seed offsets of the run are still there), not in the run.
+int lh_last_rounds(lh_context* c, int32_t lane, lh_round_info* out) {
+    if (!c || !out) return set_err(LH_E_ARG, "lh_last_rounds: null argument");
+    if (lane < 0 || lane > (int32_t)c->more.size()) return set_err(LH_E_ARG, "lh_last_rounds: no such lane");
+    lh_context* p = lane ? c->more[(size_t)lane - 1] : c;
+    RoundState& R = p->rounds;
+    memset(out, 0, sizeof *out);
+    if (R.n_rounds == 0) {
+        if (lane == 0 || !c->ran) return set_err(LH_E_ARG, "lh_last_rounds: call lh_align_resident first (and ask before the next upload, select or stage dump)");
+        return LH_OK;   // a lane that took no part in the batch: n_rounds = 0
+    }
+    if (!p->ran) return set_err(LH_E_ARG, "lh_last_rounds: call lh_align_resident first (and ask before the next upload, select or stage dump)");
+    if (!R.have_max) {   // ran whole: one part, every barcode
+        HIPCHK(hipSetDevice(p->idx->device));
+        if (!R.budget) { int rc = seed_budget(p, &R.budget); if (rc) return rc; }
+        { int rc = round_plan(p, INT64_MAX, false); if (rc) return rc; }
+        HIPCHK(hipStreamSynchronize(p->stream));
+        R.max_bc = p->plan.hdr()->max_barcode; R.max_bc_seeds = p->plan.hdr()->max_barcode_seeds;
+        if (p->plan.hdr()->n_rounds != 1 || p->plan.hdr()->total_seeds != R.total_seeds) return set_err(LH_E_HIP, "lh_last_rounds: the plan of a batch that ran whole is inconsistent");
+        R.first_bc.assign({0, p->n_bc}); R.seeds.assign(1, R.total_seeds); R.need.assign(1, seed_need(p, R.total_seeds));
+        R.have_max = true;
+    }
+    const int32_t b0 = lane && lanes_split(c) ? c->slot_cut[(size_t)c->cur_slot][(size_t)lane - 1] : 0;
+    if (b0 && R.first_bc[0] == 0) { for (int32_t& b : R.first_bc) b += b0; R.max_bc += b0; }   // (once: the arrays are the pipeline's until its next run)
+    out->n_rounds = R.n_rounds; out->max_barcode = (int32_t)R.max_bc;
+    out->first_barcode = R.first_bc.data(); out->round_seeds = R.seeds.data(); out->round_need_bytes = R.need.data();
+    out->need_bytes = seed_need(p, R.total_seeds); out->budget_bytes = R.budget; out->max_barcode_need_bytes = seed_need(p, R.max_bc_seeds);
     return LH_OK;
 }
 

@@ -99,6 +99,36 @@ static_assert(offsetof(HostPeek, one) == 0 && offsetof(HostPeek, k1.seeds) == 0 
 static_assert(offsetof(HostPeek, k6.total) == 0 && offsetof(HostPeek, k6.padded) == 8 && offsetof(HostPeek, k6.listed) == 16 && offsetof(HostPeek, k6.n_long) == 24, "k_resc_offsets: peek_host[0 .. 3]");
 static_assert(sizeof(HostPeek) == 64 && offsetof(HostPeek, prev_wave_reads) == 32, "HostPeek");
 
+// ------------------------------------------------------------------------------------------------ rounds (k_rounds.h; lh_host.inc: align_rounds)
+// lh_context::round_mem, one group: the plan's prefix array and the view of a part as a batch of its own.  Allocated when a batch first needs a plan (prefix alone:
+// lh_last_rounds after a batch that ran whole) or rounds (all four), sized by that batch, regrown as a whole when a later one is larger
+struct RoundBufs {
+    i64* prefix = nullptr;              // k_round_cost: the seeds before every barcode boundary [cap_bc + 1]
+    int32_t* v_bc_pair_off = nullptr;   // k_batch_view: the part's bc_pair_off [cap_bc + 1] ...
+    i64* v_seq_off = nullptr;           // ... seq_off [cap_reads + 1] ...
+    u64* v_seq = nullptr;               // ... and bases, 8-aligned and padded to a word [cap_bases / 8 + 8]
+    i64 cap_bc = 0, cap_reads = 0, cap_bases = 0;   // cap_reads = 0: no view yet
+};
+// k_round_plan's output in page-locked host memory the device can write: the header, then four arrays of cap_rounds + 1 words
+struct RoundPlanBlock {
+    char* p = nullptr; i64 cap_rounds = 0;
+    static size_t bytes(i64 cap) { return sizeof(RoundPlanHdr) + 4 * (size_t)(cap + 1) * sizeof(i64); }
+    RoundPlanHdr* hdr() const { return (RoundPlanHdr*)p; }
+    i64* cut_bc() const { return (i64*)(p + sizeof(RoundPlanHdr)); }   // [r]: the first barcode of part r; [n_rounds]: the batch's barcodes
+    i64* cut_pair() const { return cut_bc() + (cap_rounds + 1); }      // ... its first pair
+    i64* cut_base() const { return cut_pair() + (cap_rounds + 1); }    // ... its first base
+    i64* part_seeds() const { return cut_base() + (cap_rounds + 1); }  // [r]: the seeds of part r
+};
+// what lh_last_rounds reports on a pipeline's last lh_align_resident
+struct RoundState {
+    int n_rounds = 0;          // 0: the pipeline took no part in the last batch
+    bool have_max = false;     // max_bc / max_bc_seeds are known (a batch that ran whole: only once lh_last_rounds has asked the device)
+    i64 total_seeds = 0, budget = 0, max_bc = 0, max_bc_seeds = 0;
+    std::vector<int32_t> first_bc;
+    std::vector<i64> seeds, need;
+    void clear() { *this = RoundState(); }
+};
+
 // ------------------------------------------------------------------------------------------------ buffers cut into sections
 // lh_context::d_ext_u, K4's long queue per chain slot (pool_cap of them): a few int lists, then the units' saved state
 struct ExtUnits {
