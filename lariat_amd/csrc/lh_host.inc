@@ -95,11 +95,9 @@ struct lh_context {
     }
     int grid_smem4 = 0; PEnt* d_slab4 = nullptr; K1Counters* d_next_read = nullptr;
     // inputs
-    uint32_t* d_seq4 = nullptr;   // the selected batch's reads as a 4-bit stream (k_pack_reads), two words of padding in front
-    uint8_t* d_seq = nullptr; i64* d_seq_off = nullptr; u64* d_name_seed = nullptr; int32_t* d_bc_pair_off = nullptr; uint8_t* d_bc_do_rfa = nullptr;
-    i64 *d_cen_start = nullptr, *d_cen_end = nullptr;
-    int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false; i64 n_bases = 0; const uint32_t* q4 = nullptr;
-    int max_len = LH_MAXLEN;   // the selected batch's longest read (K1 stages its queries in that many bases' worth of LDS)
+    BatchView b;                  // the selected batch: a slot's (select_slot) or, inside align_rounds, a round's part of it
+    uint32_t* d_seq4 = nullptr;   // its reads as a 4-bit stream (k_pack_reads), two words of padding in front
+    const uint32_t* q4 = nullptr;   // d_seq4 + 2 while the index has the 4-bit text (run_front)
     // K1
     DIntv* d_intv = nullptr; DIntv* d_big_slab = nullptr; int32_t *d_big_slot = nullptr, *d_big_list = nullptr; K1BigCounts* d_big_count = nullptr; int big_cap = 0, big_base = 0;   // reads with more than LH_MAX_INTV intervals (k_smem4.h BIG)
     K1Resume* d_k1_resume = nullptr; int32_t *d_k1_todo = nullptr, *d_p2_tasks = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read->n_todo)
@@ -142,13 +140,11 @@ struct lh_context {
     float tms[LH_NSTAGE];
     int n_t = 0;
     bool resident = false, ran = false;
-    // resident input batches: slot 0 holds capacity-sized buffers allocated at creation, further slots own exact-size copies;
-    // the d_seq ... d_cen_end pointers above always name the SELECTED slot's
+    // resident input batches: slot 0 holds capacity-sized buffers allocated at creation, further slots own exact-size copies
     struct DevBatch {
-        uint8_t* seq = nullptr; i64* seq_off = nullptr; u64* name_seed = nullptr; int32_t* bc_pair_off = nullptr; uint8_t* bc_do_rfa = nullptr;
-        i64 *cen_start = nullptr, *cen_end = nullptr;
-        DevGroup mem;   // the seven arrays above
-        int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false, filled = false; i64 n_bases = 0; int max_len = LH_MAXLEN;
+        BatchView v;    // the slot's batch (pipe_upload_slot)
+        DevGroup mem;   // v's seven arrays
+        bool filled = false;
         i64 cap_bases = 0; int cap_reads = 0, cap_bc = 0;   // what the slot's own buffers hold (slots > 0)
     };
     std::deque<DevBatch> slots; std::mutex slot_mu;   // slot_mu: slots' size and `filled`, sel_slot / resident, free_later.  (A deque: growing it does not move the slots another thread holds)
@@ -270,7 +266,7 @@ static i64 first_pool_cap(const lh_context* c) {   // ~10 seeds per 150-base rea
 static i64 first_cand_cap(const lh_context* c) { return c->cap_reads * 3 > LH_POOL_FLOOR ? c->cap_reads * 3 : LH_POOL_FLOOR; }     // ~1.1 candidates/read on unique sequence
 
 static void pipe_free(lh_context* c);
-static void select_slot(lh_context* c, const lh_context::DevBatch& sl);
+static void select_slot(lh_context* c, const lh_context::DevBatch& sl) { c->b = sl.v; }
 struct CtxGuard { lh_context* c; ~CtxGuard() { if (c) pipe_free(c); } };
 
 static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* co, lh_context** out) {
@@ -307,9 +303,9 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
     DALLOC(g, c->d_seq4, c->cap_bases / 8 + 16); HIPCHK(hipMemset(c->d_seq4, 0x44, 16));
     {
         lh_context::DevBatch& s0 = c->slots.emplace_back();
-        DALLOC(s0.mem, s0.seq, c->cap_bases + 64); DALLOC(s0.mem, s0.seq_off, N + 1); DALLOC(s0.mem, s0.name_seed, max_pairs);
-        DALLOC(s0.mem, s0.bc_pair_off, c->cap_bc + 1); DALLOC(s0.mem, s0.bc_do_rfa, c->cap_bc);
-        DALLOC(s0.mem, s0.cen_start, idx->names.size()); DALLOC(s0.mem, s0.cen_end, idx->names.size());
+        DALLOC(s0.mem, s0.v.seq, c->cap_bases + 64); DALLOC(s0.mem, s0.v.seq_off, N + 1); DALLOC(s0.mem, s0.v.name_seed, max_pairs);
+        DALLOC(s0.mem, s0.v.bc_pair_off, c->cap_bc + 1); DALLOC(s0.mem, s0.v.bc_do_rfa, c->cap_bc);
+        DALLOC(s0.mem, s0.v.cen_start, idx->names.size()); DALLOC(s0.mem, s0.v.cen_end, idx->names.size());
         select_slot(c, s0);
     }
     DALLOC(g, c->d_intv, N * LH_MAX_INTV); DALLOC(g, c->d_n_intv, N);
@@ -357,12 +353,6 @@ static void pipe_free(lh_context* c) {
     delete c;
 }
 
-static void select_slot(lh_context* c, const lh_context::DevBatch& sl) {
-    c->d_seq = sl.seq; c->d_seq_off = sl.seq_off; c->d_name_seed = sl.name_seed; c->d_bc_pair_off = sl.bc_pair_off; c->d_bc_do_rfa = sl.bc_do_rfa;
-    c->d_cen_start = sl.cen_start; c->d_cen_end = sl.cen_end;
-    c->n_pairs = sl.n_pairs; c->n_reads = sl.n_reads; c->n_bc = sl.n_bc; c->has_cen = sl.has_cen; c->n_bases = sl.n_bases; c->max_len = sl.max_len;
-}
-
 static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool staged) {
     if (!c || !b || !b->seq_off || !b->seq || !b->bc_pair_off) return set_err(LH_E_ARG, "lh_batch_upload: null argument");
     if (slot < 0 || slot > 4096) return set_err(LH_E_ARG, "lh_batch_upload_slot: slot out of range");
@@ -394,6 +384,7 @@ static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool
         slp->filled = false;   // not selectable while its contents are being replaced (a failed copy leaves it so)
     }
     lh_context::DevBatch& sl = *slp;
+    BatchView& v = sl.v;
     if (slot > 0 && (nb > sl.cap_bases || n_reads > sl.cap_reads || b->n_barcodes > sl.cap_bc)) {
         // buffers of its own (slot 0 uses the capacity-sized ones), kept while the next batch fits.  hipFree waits for the whole device: from
         // the staging thread it would sit behind the kernels the upload is meant to run beside, so the old buffers are handed to the thread
@@ -403,26 +394,26 @@ static int pipe_upload_slot(lh_context* c, int32_t slot, const lh_batch* b, bool
         sl.cap_bases = 0; sl.cap_reads = 0; sl.cap_bc = 0;
         const i64 cap_bases = nb + nb / 16;
         DevGroup& g = sl.mem;
-        DALLOC(g, sl.seq, (size_t)cap_bases + 64); DALLOC(g, sl.seq_off, (size_t)n_reads + 1); DALLOC(g, sl.name_seed, (size_t)b->n_pairs);
-        DALLOC(g, sl.bc_pair_off, (size_t)b->n_barcodes + 1); DALLOC(g, sl.bc_do_rfa, (size_t)b->n_barcodes); DALLOC(g, sl.cen_start, nc); DALLOC(g, sl.cen_end, nc);
+        DALLOC(g, v.seq, (size_t)cap_bases + 64); DALLOC(g, v.seq_off, (size_t)n_reads + 1); DALLOC(g, v.name_seed, (size_t)b->n_pairs);
+        DALLOC(g, v.bc_pair_off, (size_t)b->n_barcodes + 1); DALLOC(g, v.bc_do_rfa, (size_t)b->n_barcodes); DALLOC(g, v.cen_start, nc); DALLOC(g, v.cen_end, nc);
         sl.cap_bases = cap_bases; sl.cap_reads = n_reads; sl.cap_bc = b->n_barcodes;
     }
-    sl.n_pairs = b->n_pairs; sl.n_reads = n_reads; sl.n_bc = b->n_barcodes; sl.n_bases = nb; sl.max_len = (int)lmax;
-    HIPCHK(hipMemcpyAsync(sl.seq, b->seq, (size_t)nb, hipMemcpyHostToDevice, us));
-    HIPCHK(hipMemcpyAsync(sl.seq_off, b->seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, us));
+    v.n_pairs = b->n_pairs; v.n_reads = n_reads; v.n_bc = b->n_barcodes; v.n_bases = nb; v.max_len = (int)lmax;
+    HIPCHK(hipMemcpyAsync(v.seq, b->seq, (size_t)nb, hipMemcpyHostToDevice, us));
+    HIPCHK(hipMemcpyAsync(v.seq_off, b->seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, us));
     std::vector<u64> seeds;
     const u64* ns = (const u64*)b->name_seed;
     if (!ns) { seeds.assign(b->n_pairs, 1); ns = seeds.data(); }
-    HIPCHK(hipMemcpyAsync(sl.name_seed, ns, (size_t)b->n_pairs * 8, hipMemcpyHostToDevice, us));
-    HIPCHK(hipMemcpyAsync(sl.bc_pair_off, b->bc_pair_off, (size_t)(b->n_barcodes + 1) * 4, hipMemcpyHostToDevice, us));
+    HIPCHK(hipMemcpyAsync(v.name_seed, ns, (size_t)b->n_pairs * 8, hipMemcpyHostToDevice, us));
+    HIPCHK(hipMemcpyAsync(v.bc_pair_off, b->bc_pair_off, (size_t)(b->n_barcodes + 1) * 4, hipMemcpyHostToDevice, us));
     std::vector<uint8_t> rfa;
     const uint8_t* pr = b->bc_do_rfa;
     if (!pr) { rfa.assign(b->n_barcodes, 1); pr = rfa.data(); }
-    HIPCHK(hipMemcpyAsync(sl.bc_do_rfa, pr, (size_t)b->n_barcodes, hipMemcpyHostToDevice, us));
-    sl.has_cen = b->cen_start && b->cen_end;
+    HIPCHK(hipMemcpyAsync(v.bc_do_rfa, pr, (size_t)b->n_barcodes, hipMemcpyHostToDevice, us));
+    v.has_cen = b->cen_start && b->cen_end;
     std::vector<i64> neg(nc, -1);
-    HIPCHK(hipMemcpyAsync(sl.cen_start, sl.has_cen ? b->cen_start : neg.data(), nc * 8, hipMemcpyHostToDevice, us));
-    HIPCHK(hipMemcpyAsync(sl.cen_end, sl.has_cen ? b->cen_end : neg.data(), nc * 8, hipMemcpyHostToDevice, us));
+    HIPCHK(hipMemcpyAsync(v.cen_start, v.has_cen ? b->cen_start : neg.data(), nc * 8, hipMemcpyHostToDevice, us));
+    HIPCHK(hipMemcpyAsync(v.cen_end, v.has_cen ? b->cen_end : neg.data(), nc * 8, hipMemcpyHostToDevice, us));
     HIPCHK(hipStreamSynchronize(us));
     std::lock_guard<std::mutex> g(c->slot_mu);
     sl.filled = true;
@@ -467,7 +458,7 @@ static int run_scan(lh_context* c, int n, const int32_t* in, int add, int at_lea
 
 static ExtArgs ext_args(lh_context* c) {
     ExtArgs A;
-    A.seq = c->d_seq; A.q4 = c->q4; A.seq_off = c->d_seq_off; A.seed_off = c->d_seed_off; A.chains = c->d_chains; A.cseeds = c->d_cseeds; A.n_chains = c->d_n_chains;
+    A.seq = c->b.seq; A.q4 = c->q4; A.seq_off = c->b.seq_off; A.seed_off = c->d_seed_off; A.chains = c->d_chains; A.cseeds = c->d_cseeds; A.n_chains = c->d_n_chains;
     A.sorder = c->d_srt; A.sdone = c->d_ord; A.chain_rmax = c->d_chain_rmax; A.reg_off = c->d_reg_off; A.regs = c->d_regs; A.n_regs = c->d_n_regs; A.est = c->d_ext_st;
     const ExtUnits U(c->d_ext_u, (size_t)c->pool_cap);
     A.nreg_u = U.nreg_u; A.u_read = U.u_read; A.est_u = U.est_u; A.rflag = ExtLongLists(c->d_ext_long, (size_t)c->cap_reads).rflag;
@@ -480,7 +471,7 @@ static ExtArgs ext_args(lh_context* c) {
 // second chance's slab (BIG), else the list the pass works from (k_smem_first's reads, pass 2's tasks; none: every read)
 template <int PASS, bool BIG, int QW = 32> static void smem_pass(lh_context* c, const DIndex& ix4, const DOpts& o, int N, int grid, const K1Big& big) {
     int32_t* const next = BIG ? &c->d_next_read->big_pass[PASS - 1] : &c->d_next_read->pass[PASS - 1];
-    LH_LAUNCH((k_smem_pass<PASS, BIG, QW>), grid, 64, c->stream, ix4, o, N, c->d_seq, c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, next, c->d_ctr, big);
+    LH_LAUNCH((k_smem_pass<PASS, BIG, QW>), grid, 64, c->stream, ix4, o, N, c->b.seq, c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_slab4, next, c->d_ctr, big);
 }
 
 // K1's second chance: the reads whose intervals outgrew their LH_MAX_INTV regular slots run the three passes again into slots of the big slab
@@ -509,12 +500,12 @@ static int peek_seed_total(lh_context* c, int N) {
 
 static inline int ext_long_min(int N);   // (lh_host_stage2.inc)
 static int run_front(lh_context* c, const DOpts& o, int& t) {
-    int N = c->n_reads;
+    int N = c->b.n_reads;
     const DIndex& ix = c->idx->d;
     HIPCHK(hipMemsetAsync(c->d_ctr, 0, sizeof(DCounters) * LH_CTR_SLOTS, c->stream));
     const uint32_t* q4 = nullptr;
     if (ix.tn) {   // the diagonal scans of K3 / K4 compare eight bases at a time against the 4-bit text
-        LH_LAUNCH(k_pack_reads, 4096, 256, c->stream, (const uint8_t*)c->d_seq, c->n_bases, c->d_seq4 + 2);
+        LH_LAUNCH(k_pack_reads, 4096, 256, c->stream, (const uint8_t*)c->b.seq, c->b.n_bases, c->d_seq4 + 2);
         q4 = c->d_seq4 + 2;
     }
     c->q4 = q4;
@@ -528,13 +519,13 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         const int g3 = (N + 63) / 64 < 2 * c->grid_smem4 ? (N + 63) / 64 : 2 * c->grid_smem4;   // pass 3 keeps no interval lists: the slab is not touched
         T_BEGIN("k_smem4");
         // every read's first bwt_smem1a call in lockstep, one thread per read; what it does not settle goes on in the state machine
-        LH_LAUNCH(k_smem_first, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_k1_resume, c->d_k1_todo, &c->d_next_read->n_todo, c->d_ctr);
+        LH_LAUNCH(k_smem_first, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_k1_resume, c->d_k1_todo, &c->d_next_read->n_todo, c->d_ctr);
 #ifdef LH_K1_TRACE
         K1Trace trace;
         { int rc = k1_trace_begin(c, trace, g4); if (rc) return rc; }
 #endif
         // the instance whose query staging holds the batch's longest read: the LDS it leaves is the lists' ring (k_smem4.h: LH_K1_QW_SMALL)
-        const bool qw_small = c->max_len <= 8 * LH_K1_QW_SMALL;
+        const bool qw_small = c->b.max_len <= 8 * LH_K1_QW_SMALL;
         if (qw_small) smem_pass<1, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, first);
         else smem_pass<1, false>(c, ix4, o, N, g4, first);
         T_END();
@@ -560,7 +551,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
 #endif
         T_BEGIN("k_smem4_p3");
         if (o.max_mem_intv > 0 && q4)   // forward-only walks: one thread per read, in lockstep
-            LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->d_seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr);
+            LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr);
         else if (o.max_mem_intv > 0)
             smem_pass<3, false>(c, ix4, o, N, g3, nobig);
         T_END();
@@ -641,7 +632,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
             // (r06) the three instances take disjoint reads of the list (by seed count) and share nothing but the list of what they leave: side by side on three streams
             // (mixed input: 22.0 -> 20.5 ms; each instance alone already holds most of the waves its LDS use allows)
 #define LH_K3_CL(CAP_, GRID_, LO_, LAST_, ST_)                                                                                                                         \
-            LH_LAUNCH((k_chain_cl<CAP_>), N < (GRID_) ? N : (GRID_), 64, ST_, ix, o, (const i64*)c->d_seq_off, (const i64*)c->d_seed_off, c->pool_cap, (const DSeed*)c->d_seeds, \
+            LH_LAUNCH((k_chain_cl<CAP_>), N < (GRID_) ? N : (GRID_), 64, ST_, ix, o, (const i64*)c->b.seq_off, (const i64*)c->d_seed_off, c->pool_cap, (const DSeed*)c->d_seeds, \
                       (const int32_t*)c->d_s_rid, (const int32_t*)c->d_l_rep, c->d_chains, c->d_cseeds, c->d_n_chains, c->d_status, wlist, wcount, LO_, LAST_, c->d_aln_ci, fb_count)
             HIPCHK(hipEventRecord(c->ev_fork, c->stream));
             HIPCHK(hipStreamWaitEvent(c->aux[1], c->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(c->aux[2], c->ev_fork, 0));
@@ -662,7 +653,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
                     fprintf(stderr, "[lh] K3: %d reads listed for the wave kernels, %d of them left to k_chain by k_chain_cl\n", nl, nf);
             }
         }
-        LH_LAUNCH(k_chain, N < 16384 ? N : 16384, 64, c->stream, ix, o, N, c->d_seq_off, c->d_seed_off, c->pool_cap, c->d_seeds, c->d_s_rid, c->d_l_rep, c->d_s_next, c->d_ct,
+        LH_LAUNCH(k_chain, N < 16384 ? N : 16384, 64, c->stream, ix, o, N, c->b.seq_off, c->d_seed_off, c->pool_cap, c->d_seeds, c->d_s_rid, c->d_l_rep, c->d_s_next, c->d_ct,
                   c->d_ord, c->d_srt, c->d_chains, c->d_cseeds, c->d_n_chains, c->d_status, wlist, wcount);
     }
     T_END();
@@ -694,14 +685,34 @@ static int round_mem_for(lh_context* c, int n_bc, bool view, i64 n_reads, i64 n_
 }
 // the selected batch's seeds (d_seed_off: k_scan_seeds has run) cut into parts within `budget`: the plan in c->plan once the stream is synchronised
 static int round_plan(lh_context* c, i64 budget, bool view) {
-    { int rc = round_mem_for(c, c->n_bc, view, c->n_reads, c->n_bases); if (rc) return rc; }
-    LH_LAUNCH(k_round_cost, (c->n_bc + 256) / 256, 256, c->stream, c->n_bc, (const int32_t*)c->d_bc_pair_off, (const i64*)c->d_seed_off, c->rb.prefix);
-    LH_LAUNCH(k_round_plan, 1, 64, c->stream, c->n_bc, (const i64*)c->rb.prefix, (const int32_t*)c->d_bc_pair_off, (const i64*)c->d_seq_off, budget, seed_fixed_slots(c),
+    { int rc = round_mem_for(c, c->b.n_bc, view, c->b.n_reads, c->b.n_bases); if (rc) return rc; }
+    LH_LAUNCH(k_round_cost, (c->b.n_bc + 256) / 256, 256, c->stream, c->b.n_bc, (const int32_t*)c->b.bc_pair_off, (const i64*)c->d_seed_off, c->rb.prefix);
+    LH_LAUNCH(k_round_plan, 1, 64, c->stream, c->b.n_bc, (const i64*)c->rb.prefix, (const int32_t*)c->b.bc_pair_off, (const i64*)c->b.seq_off, budget, seed_fixed_slots(c),
               LH_SEED_POOL_BYTES, (int)c->plan.cap_rounds, c->plan.hdr(), c->plan.cut_bc(), c->plan.cut_pair(), c->plan.cut_base(), c->plan.part_seeds(), c->d_wd);
     return LH_OK;
 }
 
+// Part r of the plan as a batch of its own, once k_batch_view has filled the round buffers: its reads and its barcodes' pair offsets are the buffers' copies
+// (they begin at 0), its name seeds and inference flags the whole batch's from the part's first pair and barcode on.  What is per contig or chooses a kernel instance
+// it inherits from the whole batch: has_cen and the centromere arrays, and max_len — K1's query-staging instance stays the one the whole batch chose
+static BatchView part_view(const BatchView& whole, const RoundBufs& rb, const RoundPlanBlock& P, i64 r) {
+    const i64 b0 = P.cut_bc()[r], p0 = P.cut_pair()[r];
+    BatchView v = whole;
+    v.seq = (uint8_t*)rb.v_seq; v.seq_off = rb.v_seq_off; v.bc_pair_off = rb.v_bc_pair_off;
+    v.name_seed = whole.name_seed + p0; v.bc_do_rfa = whole.bc_do_rfa + b0;
+    v.n_bc = (int)(P.cut_bc()[r + 1] - b0); v.n_pairs = (int)(P.cut_pair()[r + 1] - p0); v.n_reads = 2 * v.n_pairs; v.n_bases = P.cut_base()[r + 1] - P.cut_base()[r];
+    return v;
+}
+
+// an error return may come between a fork onto an auxiliary stream (K3's cluster kernels, K4's wave kernels beside the rounds, K6's long-list replay, K8's routed
+// barcodes) and its join: nothing of the call may still be running on the context's buffers when the caller frees or reuses them
+static void quiesce(lh_context* c) {
+    for (int i = 0; i < 3; ++i) hipStreamSynchronize(c->aux[i]);
+    hipStreamSynchronize(c->stream);
+}
+
 static int merge_results(lh_result* a, lh_result* b, lh_result** out);   // (lh_lanes.inc)
+static int merge_into(lh_result*& acc, lh_result* part);                 // (lh_lanes.inc)
 static int pipe_download(lh_context* c, lh_result** out);                // (lh_host_stage2.inc)
 struct TimeSums {   // per-kernel times summed over the rounds, in the order of their first appearance
     const char* names[LH_NSTAGE]; float ms[LH_NSTAGE]; int n = 0;
@@ -730,7 +741,7 @@ static int align_rounds(lh_context* c, const DOpts& o, int t) {
     HIPCHK(hipEventRecord(c->ev[t], c->stream));
     const i64 total = c->rounds.total_seeds;
     // the view's buffers take HBM too: with the budget read from the free memory, plan after they exist
-    { int rc = round_mem_for(c, c->n_bc, true, c->n_reads, c->n_bases); if (rc) return rc; }
+    { int rc = round_mem_for(c, c->b.n_bc, true, c->b.n_reads, c->b.n_bases); if (rc) return rc; }
     i64 budget = 0;
     { int rc = seed_budget(c, &budget); if (rc) return rc; }
     HIPCHK(hipEventRecord(c->ev[LH_NSTAGE - 1], c->stream));
@@ -746,8 +757,8 @@ static int align_rounds(lh_context* c, const DOpts& o, int t) {
     if (n_rounds == 0)
         return set_err(LH_E_CAPACITY, "barcode " + std::to_string(R.max_bc) + " has " + std::to_string(R.max_bc_seeds) + " seeds: their workspace (" + std::to_string(seed_need(c, R.max_bc_seeds)) +
                                           " bytes) does not fit the budget of " + std::to_string(budget) + " bytes (seed_budget_kb, or the HBM that is free), and a barcode is never split");
-    bool ok = n_rounds > 0 && n_rounds <= c->n_bc && P.hdr()->total_seeds == total && P.cut_bc()[0] == 0 && P.cut_bc()[n_rounds] == c->n_bc && P.cut_pair()[n_rounds] == c->n_pairs &&
-              P.cut_base()[n_rounds] == c->n_bases;
+    bool ok = n_rounds > 0 && n_rounds <= c->b.n_bc && P.hdr()->total_seeds == total && P.cut_bc()[0] == 0 && P.cut_bc()[n_rounds] == c->b.n_bc && P.cut_pair()[n_rounds] == c->b.n_pairs &&
+              P.cut_base()[n_rounds] == c->b.n_bases;
     for (i64 r = 0; ok && r < n_rounds; ++r)
         ok = P.cut_bc()[r] < P.cut_bc()[r + 1] && P.cut_pair()[r] < P.cut_pair()[r + 1] && P.cut_base()[r] <= P.cut_base()[r + 1] && seed_need(c, P.part_seeds()[r]) <= budget;
     if (!ok) return set_err(LH_E_HIP, "the round plan is inconsistent (k_round_plan, watchdog slot " + std::to_string(LH_WD_ROUND_PLAN) + ")");
@@ -760,35 +771,32 @@ static int align_rounds(lh_context* c, const DOpts& o, int t) {
     const bool host_pending = c->dl_pending;
     std::function<int(lh_result**)> host_finish;
     if (host_pending) { HIPCHK(hipEventSynchronize(c->ev_dl)); host_finish = std::move(c->dl_finish); c->dl_pending = false; }
-    struct Whole {   // the batch's own selection, back in place however this ends
-        lh_context* c; uint8_t* seq; i64* seq_off; u64* name_seed; int32_t* bc_pair_off; uint8_t* bc_do_rfa; int n_pairs, n_reads, n_bc; i64 n_bases;
-        bool pending; std::function<int(lh_result**)>* finish;
-        ~Whole() {
-            c->d_seq = seq; c->d_seq_off = seq_off; c->d_name_seed = name_seed; c->d_bc_pair_off = bc_pair_off; c->d_bc_do_rfa = bc_do_rfa;
-            c->n_pairs = n_pairs; c->n_reads = n_reads; c->n_bc = n_bc; c->n_bases = n_bases; c->in_round = false;
-            if (pending) { c->dl_pending = true; c->dl_finish = std::move(*finish); }
+    const BatchView whole = c->b;
+    struct Restore {   // the batch's own selection and the host's pending download, back in place however this ends
+        lh_context* c; const BatchView& whole; bool pending; std::function<int(lh_result**)>& finish;
+        ~Restore() {
+            c->b = whole; c->in_round = false;
+            if (pending) { c->dl_pending = true; c->dl_finish = std::move(finish); }
         }
-    } whole{c, c->d_seq, c->d_seq_off, c->d_name_seed, c->d_bc_pair_off, c->d_bc_do_rfa, c->n_pairs, c->n_reads, c->n_bc, c->n_bases, host_pending, &host_finish};
+    } restore{c, whole, host_pending, host_finish};
     c->in_round = true;
     lh_result* acc = nullptr;
     for (i64 r = 0; r < n_rounds; ++r) {
-        const int b0 = (int)P.cut_bc()[r], b1 = (int)P.cut_bc()[r + 1], p0 = (int)P.cut_pair()[r], p1 = (int)P.cut_pair()[r + 1];
-        const i64 s0 = P.cut_base()[r], s1 = P.cut_base()[r + 1];
-        const int nb = b1 - b0, np = p1 - p0, nr = 2 * np;
+        const int b0 = (int)P.cut_bc()[r], p0 = (int)P.cut_pair()[r];
+        const i64 s0 = P.cut_base()[r];
+        const BatchView part = part_view(whole, c->rb, P, r);
         int rt = 0;
         HIPCHK(hipEventRecord(c->ev[LH_NSTAGE - 1], c->stream));
         {
-            const i64 work = (s1 - s0) / 8 > nr ? (s1 - s0) / 8 : nr;
-            LH_LAUNCH(k_batch_view, (int)(work / 256 + 1 < 4096 ? work / 256 + 1 : 4096), 256, c->stream, nb, nr, s1 - s0, b0, p0, s0, (const int32_t*)whole.bc_pair_off,
+            const i64 work = part.n_bases / 8 > part.n_reads ? part.n_bases / 8 : part.n_reads;
+            LH_LAUNCH(k_batch_view, (int)(work / 256 + 1 < 4096 ? work / 256 + 1 : 4096), 256, c->stream, part.n_bc, part.n_reads, part.n_bases, b0, p0, s0, (const int32_t*)whole.bc_pair_off,
                       (const i64*)whole.seq_off, (const uint8_t*)whole.seq, c->rb.v_bc_pair_off, c->rb.v_seq_off, c->rb.v_seq);
         }
         HIPCHK(hipEventRecord(c->ev[LH_NSTAGE], c->stream));
-        c->d_seq = (uint8_t*)c->rb.v_seq; c->d_seq_off = c->rb.v_seq_off; c->d_bc_pair_off = c->rb.v_bc_pair_off;
-        c->d_name_seed = whole.name_seed + p0; c->d_bc_do_rfa = whole.bc_do_rfa + b0;
-        c->n_pairs = np; c->n_reads = nr; c->n_bc = nb; c->n_bases = s1 - s0;
+        c->b = part;
         int rc = run_front(c, o, rt);
         if (!rc) rc = stage2_run(c, o, rt);
-        lh_result* part = nullptr;
+        lh_result* res = nullptr;
         if (!rc) {
             hipError_t e = hipEventRecord(c->ev[rt], c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -798,20 +806,14 @@ static int align_rounds(lh_context* c, const DOpts& o, int t) {
         if (!rc) { float v = 0; hipEventElapsedTime(&v, c->ev[LH_NSTAGE - 1], c->ev[LH_NSTAGE]); sums.add("k_batch_view", v); }
         if (!rc) {
             c->ran = true;
-            rc = pipe_download(c, &part);   // (the watchdog slots are read and cleared with every part's result)
+            rc = pipe_download(c, &res);   // (the watchdog slots are read and cleared with every part's result)
             c->ran = false;
             if (rc) rc = set_err(rc, "round " + std::to_string(r) + " of " + std::to_string(n_rounds) + " (its reads start at read " + std::to_string(2 * (i64)p0) + " of the batch): " + g_err);
         }
-        if (!rc && acc) {
-            lh_result* m = nullptr;
-            rc = merge_results(acc, part, &m);
-            lh_result_free(acc); lh_result_free(part);
-            acc = m; part = nullptr;
-        } else if (!rc) acc = part;
+        if (!rc) rc = merge_into(acc, res);
         if (rc) {
             const std::string why = g_err;
-            for (int i = 0; i < 3; ++i) hipStreamSynchronize(c->aux[i]);
-            hipStreamSynchronize(c->stream);
+            quiesce(c);
             if (acc) lh_result_free(acc);
             return set_err(rc, why);
         }
@@ -848,13 +850,7 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     const bool in_rounds = rc == LH_NEED_ROUNDS;
     if (in_rounds) rc = align_rounds(c, o, t);
     else if (!rc) rc = stage2_run(c, o, t);
-    if (rc) {
-        // an error return may come between a fork onto the auxiliary stream (K4's wave kernels beside the rounds, K6's long-list replay) and its join: nothing
-        // of this call may still be running on the context's buffers when the caller frees or reuses them
-        for (int i = 0; i < 3; ++i) hipStreamSynchronize(c->aux[i]);
-        hipStreamSynchronize(c->stream);
-        return rc;
-    }
+    if (rc) { quiesce(c); return rc; }
     if (!in_rounds) {
         HIPCHK(hipEventRecord(c->ev[t], c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -892,11 +888,12 @@ template <class T> static int d2h(std::vector<T>& v, const T* d, size_t n) {
 #define D2H(v, d, n) do { int rc_ = d2h(v, d, (size_t)(n)); if (rc_) return rc_; } while (0)
 
 static int stage2_dump_regs(lh_context* c, DumpArenaH* A);
+static bool lanes_split(const lh_context* c);   // (lh_lanes.inc)
 
 int lh_stage_dump_resident(lh_context* c, const lh_opts* opts, lh_stage_dump** out) {
     if (!c || !opts || !out) return set_err(LH_E_ARG, "lh_stage_dump_resident: null argument");
     {   // the dump shows mem_align1_core's output, i.e. BEFORE mate rescue: rerun the front half only
-        if (!c->more.empty() && (size_t)c->cur_slot < c->slot_cut.size() && !c->slot_cut[(size_t)c->cur_slot].empty())
+        if (lanes_split(c))
             return set_err(LH_E_ARG, "lh_stage_dump_resident: the resident batch is split over several lanes (create the context with lanes = 1 for stage dumps)");
         c->dump_stop_after_dedup = true;
         int rc = pipe_align(c, opts);
@@ -904,7 +901,7 @@ int lh_stage_dump_resident(lh_context* c, const lh_opts* opts, lh_stage_dump** o
         c->ran = false;
         if (rc) return rc;
     }
-    int N = c->n_reads;
+    int N = c->b.n_reads;
     DumpArenaH* A = new DumpArenaH();
     std::vector<int32_t> n_intv, n_chains, s_rid, status;
     std::vector<DIntv> intv;

@@ -72,22 +72,57 @@ static int alloc_cand_pools(lh_context* c, i64 C) {
     return LH_OK;
 }
 
+// K6 once its jobs exist (the emitting pass of rescue_dir; lh_diag_rescue_sw's own): which rows of its window a job's forward pass has to run (r06, k_rescue3.h:
+// k_resc_cert, a certificate per job and no DP; not with full), the jobs in the order (striping, rows) — an order by striping alone that the emitting pass left is
+// replaced — the forward Smith-Waterman, the jobs that reached min_seed_len in the order of THEIR striping, the reverse Smith-Waterman.  order: `padded` ints, what
+// the first order takes (fewer jobs after the certificates, the same padding); order2: cap2 ints, every job with each bucket padded to 8.  meta: bstart / hist2 cleared
+static int rescue_sw(hipStream_t st, const DIndex& ix, const DOpts& o, i64 total, RJob* jobs, const uint8_t* seq, RMeta* meta, int32_t* keys, int32_t* order, i64 padded,
+                     int32_t* order2, i64 cap2, DCounters* ctr, bool full, int weaken) {
+    const int gb = (int)((total + 4095) / 4096 < 1024 ? (total + 4095) / 4096 : 1024), minsc = o.min_seed_len * o.a;
+    int32_t *const hist1 = keys, *const bstart1 = keys + LH_RC_KEYS, *const bcur1 = keys + 2 * LH_RC_KEYS;
+    if (!full) LH_LAUNCH(k_resc_cert, (int)((total + 15) / 16 < 65536 ? (total + 15) / 16 : 65536), 64, st, ix, o, total, jobs, seq, weaken);
+    HIPCHK(hipMemsetAsync(hist1, 0, sizeof(int32_t) * LH_RC_KEYS, st));
+    LH_LAUNCH((k_resc_bucket1<false>), gb, 256, st, total, (const RJob*)jobs, hist1, bcur1, (const int32_t*)bstart1, order, ctr);
+    LH_LAUNCH(k_resc_offsets1, 1, 1, st, meta, (const int32_t*)hist1, bstart1, bcur1, (i64*)nullptr);
+    HIPCHK(hipMemsetAsync(order, 0xff, (size_t)padded * 4, st));
+    LH_LAUNCH((k_resc_bucket1<true>), gb, 256, st, total, (const RJob*)jobs, hist1, bcur1, (const int32_t*)bstart1, order, ctr);
+    LH_LAUNCH((k_resc_sw<false>), (int)(padded / 8), 64, st, ix, o, jobs, (const int32_t*)order, seq, meta);
+    LH_LAUNCH((k_resc_bucket2<false>), gb, 256, st, total, (const RJob*)jobs, minsc, meta, order2);
+    LH_LAUNCH(k_resc_offsets, 1, 1, st, meta, 1, (i64*)nullptr, (const i64*)nullptr);
+    HIPCHK(hipMemsetAsync(order2, 0xff, (size_t)cap2 * 4, st));
+    LH_LAUNCH((k_resc_bucket2<true>), gb, 256, st, total, (const RJob*)jobs, minsc, meta, order2);
+    LH_LAUNCH((k_resc_sw<true>), (int)(cap2 / 8), 64, st, ix, o, jobs, (const int32_t*)order2, seq, meta);
+    return LH_OK;
+}
+
 // K6 (k_rescue2.h): per direction, the attempts that need a Smith-Waterman become jobs for the packed systolic kernel; a wave per pair then
 // replays gobwa.go's loop with their results.  One host round trip per direction: the job arrays follow the batch.
 template <int DIR> static int rescue_dir(lh_context* c, const DOpts& o, const DIndex& ix) {
-    const int P = c->n_pairs;
+    const int P = c->b.n_pairs;
+    const uint8_t* const seq = c->b.seq;
+    // the enumeration, a lane per pair and a wave per heavy pair; emit (std::true_type, after the scan of the counts): write the jobs and their places in the order array
+    auto resc_enum = [&](auto emit, int grid) {
+        constexpr bool EMIT = decltype(emit)::value;
+        const i64* const job_off = EMIT ? c->d_rjob_off : nullptr; RJob* const jobs = EMIT ? c->d_rjobs : nullptr; int32_t* const order = EMIT ? c->d_rorder : nullptr;
+        LH_LAUNCH((k_resc_enum<DIR, EMIT>), grid, 256, c->stream, ix, o, P, seq, (const i64*)c->b.seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
+                  (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, job_off, jobs, order, c->d_rmeta, c->d_aln_r, c->d_rheavy);
+        LH_LAUNCH((k_resc_enum_w<DIR, EMIT>), P < 8192 ? P : 8192, 64, c->stream, ix, o, P, seq, (const i64*)c->b.seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
+                  (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, job_off, jobs, order, c->d_rmeta, c->d_aln_r, (const int32_t*)c->d_rheavy);
+    };
+    // the replay, a wave per listed pair; cap (std::integral_constant): the instance by the list entries its LDS holds
+    auto resc_apply = [&](auto cap, int grid, hipStream_t st) {
+        LH_LAUNCH((k_resc_apply<DIR, decltype(cap)::value>), grid, 64, st, ix, o, P, seq, (const i64*)c->b.seq_off, (const i64*)c->d_reg_off, c->d_regs,
+                  c->d_regs_tmp, c->d_ia, c->d_n_regs, (const int32_t*)c->d_best, (const uint8_t*)c->d_reg_clean, c->d_ctr, (const int32_t*)c->d_aln_r, c->d_rmeta, (const int32_t*)c->d_rnj,
+                  (const i64*)c->d_rjob_off, (const RJob*)c->d_rjobs);
+    };
     HIPCHK(hipMemsetAsync(c->d_rmeta, 0, sizeof(RMeta), c->stream));
-    LH_LAUNCH((k_resc_enum<DIR, false>), (P + 255) / 256, 256, c->stream, ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
-              (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, (const i64*)nullptr, (RJob*)nullptr, (int32_t*)nullptr, c->d_rmeta, c->d_aln_r, c->d_rheavy);
-    LH_LAUNCH((k_resc_enum_w<DIR, false>), P < 8192 ? P : 8192, 64, c->stream, ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
-              (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, (const i64*)nullptr, (RJob*)nullptr, (int32_t*)nullptr, c->d_rmeta, c->d_aln_r, (const int32_t*)c->d_rheavy);
+    resc_enum(std::false_type(), (P + 255) / 256);
     { int rc = run_scan(c, P, c->d_rnj, 0, 0, c->d_rjob_off); if (rc) return rc; }
     LH_LAUNCH(k_resc_offsets, 1, 1, c->stream, c->d_rmeta, 0, &c->h_peek->k6.total, (const i64*)(c->d_rjob_off + P));
     HIPCHK(hipStreamSynchronize(c->stream));
     const i64 total = c->h_peek->k6.total, padded = c->h_peek->k6.padded, listed = c->h_peek->k6.listed, n_long = c->h_peek->k6.n_long;
     if (listed == 0) return LH_OK;
     if (total > 0) {
-        const i64 cap2 = total + 8 * LH_RJ_NB;   // the reverse passes' order array: at most every job, each bucket padded to 8
         if (total > c->rjob_cap) {
             DevGroup& g = c->rjob_mem;
             g.release(); c->rjob_cap = 0;
@@ -96,40 +131,19 @@ template <int DIR> static int rescue_dir(lh_context* c, const DOpts& o, const DI
             c->rjob_cap = cap;
         }
         HIPCHK(hipMemsetAsync(c->d_rorder, 0xff, (size_t)padded * 4, c->stream));
-        LH_LAUNCH((k_resc_enum<DIR, true>), (int)((listed + 255) / 256), 256, c->stream, ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
-                  (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, (const i64*)c->d_rjob_off, c->d_rjobs, c->d_rorder, c->d_rmeta, c->d_aln_r, c->d_rheavy);
-        LH_LAUNCH((k_resc_enum_w<DIR, true>), P < 8192 ? P : 8192, 64, c->stream, ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, (const DReg*)c->d_regs,
-                  (const int32_t*)c->d_n_regs, (const int32_t*)c->d_best, c->d_rnj, (const i64*)c->d_rjob_off, c->d_rjobs, c->d_rorder, c->d_rmeta, c->d_aln_r, (const int32_t*)c->d_rheavy);
-        const int gb = (int)((total + 4095) / 4096 < 1024 ? (total + 4095) / 4096 : 1024);
-        // (r06, k_rescue3.h) which rows of its window a job's forward pass has to run (k_resc_cert: a certificate per job, no DP), then the jobs in the order
-        // (striping, rows): the emitting pass's order by striping alone is replaced.  The order array's size is that of the first order (fewer jobs, same padding).
-        if (!(c->flags & LH_F_RESCUE_FULL))
-            LH_LAUNCH(k_resc_cert, (int)((total + 15) / 16 < 65536 ? (total + 15) / 16 : 65536), 64, c->stream, ix, o, total, c->d_rjobs, (const uint8_t*)c->d_seq, 0);
-        HIPCHK(hipMemsetAsync(c->d_rkeys, 0, sizeof(int32_t) * LH_RC_KEYS, c->stream));
-        LH_LAUNCH((k_resc_bucket1<false>), gb, 256, c->stream, total, (const RJob*)c->d_rjobs, c->d_rkeys, c->d_rkeys + 2 * LH_RC_KEYS, (const int32_t*)(c->d_rkeys + LH_RC_KEYS), c->d_rorder, c->d_ctr);
-        LH_LAUNCH(k_resc_offsets1, 1, 1, c->stream, c->d_rmeta, (const int32_t*)c->d_rkeys, c->d_rkeys + LH_RC_KEYS, c->d_rkeys + 2 * LH_RC_KEYS, (i64*)nullptr);
-        HIPCHK(hipMemsetAsync(c->d_rorder, 0xff, (size_t)padded * 4, c->stream));
-        LH_LAUNCH((k_resc_bucket1<true>), gb, 256, c->stream, total, (const RJob*)c->d_rjobs, c->d_rkeys, c->d_rkeys + 2 * LH_RC_KEYS, (const int32_t*)(c->d_rkeys + LH_RC_KEYS), c->d_rorder, c->d_ctr);
-        LH_LAUNCH((k_resc_sw<false>), (int)(padded / 8), 64, c->stream, ix, o, c->d_rjobs, (const int32_t*)c->d_rorder, (const uint8_t*)c->d_seq, c->d_rmeta);
-        LH_LAUNCH((k_resc_bucket2<false>), gb, 256, c->stream, total, (const RJob*)c->d_rjobs, o.min_seed_len * o.a, c->d_rmeta, c->d_rorder2);
-        LH_LAUNCH(k_resc_offsets, 1, 1, c->stream, c->d_rmeta, 1, (i64*)nullptr, (const i64*)nullptr);
-        HIPCHK(hipMemsetAsync(c->d_rorder2, 0xff, (size_t)cap2 * 4, c->stream));
-        LH_LAUNCH((k_resc_bucket2<true>), gb, 256, c->stream, total, (const RJob*)c->d_rjobs, o.min_seed_len * o.a, c->d_rmeta, c->d_rorder2);
-        LH_LAUNCH((k_resc_sw<true>), (int)(cap2 / 8), 64, c->stream, ix, o, c->d_rjobs, (const int32_t*)c->d_rorder2, (const uint8_t*)c->d_seq, c->d_rmeta);
-        LH_LAUNCH(k_resc_cells2, gb, 256, c->stream, total, (const RJob*)c->d_rjobs, o.min_seed_len * o.a, c->d_ctr);
+        resc_enum(std::true_type(), (int)((listed + 255) / 256));
+        { int rc = rescue_sw(c->stream, ix, o, total, c->d_rjobs, seq, c->d_rmeta, c->d_rkeys, c->d_rorder, padded, c->d_rorder2, total + 8 * LH_RJ_NB, c->d_ctr,
+                             (c->flags & LH_F_RESCUE_FULL) != 0, 0); if (rc) return rc; }
+        LH_LAUNCH(k_resc_cells2, (int)((total + 4095) / 4096 < 1024 ? (total + 4095) / 4096 : 1024), 256, c->stream, total, (const RJob*)c->d_rjobs, o.min_seed_len * o.a, c->d_ctr);
     }
     // the few pairs with long lists (LH_RA_CAP_BIG entries of LDS per wave) beside the others: disjoint pairs, and a single long pair can take as long as all the short ones
     if (n_long > 0) {
-    HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->aux[0], c->ev_fork, 0));
-    LH_LAUNCH((k_resc_apply<DIR, LH_RA_CAP_BIG>), (int)(listed < 2048 ? listed : 2048), 64, c->aux[0], ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, c->d_regs,
-              c->d_regs_tmp, c->d_ia, c->d_n_regs, (const int32_t*)c->d_best, (const uint8_t*)c->d_reg_clean, c->d_ctr, (const int32_t*)c->d_aln_r, c->d_rmeta, (const int32_t*)c->d_rnj,
-              (const i64*)c->d_rjob_off, (const RJob*)c->d_rjobs);
-    HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
+        HIPCHK(hipEventRecord(c->ev_fork, c->stream));
+        HIPCHK(hipStreamWaitEvent(c->aux[0], c->ev_fork, 0));
+        resc_apply(std::integral_constant<int, LH_RA_CAP_BIG>(), (int)(listed < 2048 ? listed : 2048), c->aux[0]);
+        HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
     }
-    LH_LAUNCH((k_resc_apply<DIR, LH_RA_CAP>), (int)(listed < 16384 ? listed : 16384), 64, c->stream, ix, o, P, (const uint8_t*)c->d_seq, (const i64*)c->d_seq_off, (const i64*)c->d_reg_off, c->d_regs,
-              c->d_regs_tmp, c->d_ia, c->d_n_regs, (const int32_t*)c->d_best, (const uint8_t*)c->d_reg_clean, c->d_ctr, (const int32_t*)c->d_aln_r, c->d_rmeta, (const int32_t*)c->d_rnj,
-              (const i64*)c->d_rjob_off, (const RJob*)c->d_rjobs);
+    resc_apply(std::integral_constant<int, LH_RA_CAP>(), (int)(listed < 16384 ? listed : 16384), c->stream);
     if (n_long > 0) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
     return LH_OK;
 }
@@ -159,8 +173,22 @@ static inline int ext_long_min(int N) { const int a = N / LH_EXT_LONG_DIV; retur
 #ifndef LH_EXT_LONG_GROUP
 #define LH_EXT_LONG_GROUP 4      // rounds between two looks at the queue
 #endif
+// k_extend, the wave-per-read kernel (k_extend.h), for the reads of a list on the device (range: its bounds); no list: every read of the batch, a wave each.
+// count: the chains of these reads are not in the counters yet
+static void launch_extend(lh_context* c, const DOpts& o, hipStream_t st, const int32_t* list, const int32_t* range, int count) {
+    const int N = c->b.n_reads;
+    LH_LAUNCH(k_extend, list && N > 16384 ? 16384 : N, 64, st, c->idx->d, o, N, list, range, c->b.seq, c->q4, c->b.seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
+              c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, count);
+}
+// the jobs queued in J->count[cur] (keys and list: jkey, jlist) sorted by kind and size into jorder, for k_ext_round; other: the queue the round fills (the long queue's
+// two take turns), or -1
+static void ext_sort_jobs(hipStream_t st, int grid, DExtJobs* J, int cur, int other, const int32_t* jkey, const int32_t* jlist, int32_t* jorder) {
+    LH_LAUNCH(k_extj_count, grid, 256, st, (const int32_t*)(J->count + cur), jkey, J);
+    LH_LAUNCH(k_extj_offsets, 1, 256, st, J, cur, other);
+    LH_LAUNCH(k_extj_scatter, grid, 256, st, (const int32_t*)(J->count + cur), jkey, jlist, J, jorder);
+}
 static int ext_long_queue(lh_context* c, const DOpts& o, hipStream_t st) {
-    const int N = c->n_reads;
+    const int N = c->b.n_reads;
     const DIndex& ix = c->idx->d;
     const ExtLongLists Q(c->d_ext_long, (size_t)c->cap_reads);
     const ExtUnits U(c->d_ext_u, (size_t)c->pool_cap);
@@ -173,8 +201,7 @@ static int ext_long_queue(lh_context* c, const DOpts& o, hipStream_t st) {
     LH_LAUNCH(k_ext_prep, gw, 64, st, ix, o, (const int32_t*)c->d_aln_r, (const int32_t*)c->d_ext_jobs->wave_range, ext_long_min(N), A, c->d_srt, c->d_chain_rmax,
               U.u_read, Q.long_list, J->wave_range + 1, Q.fb_list, J->heavy_range + 1, U.ulist, J->count, c->d_ctr);
     // (before the host looks at the queue: with few listed reads — the usual batch — this is all there is, and it should start at once)
-    LH_LAUNCH(k_extend, gw, 64, st, ix, o, N, (const int32_t*)Q.fb_list, (const int32_t*)J->heavy_range, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
-              c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, 1);
+    launch_extend(c, o, st, Q.fb_list, J->heavy_range, 1);
     LH_LAUNCH(k_ext_round0, 2560, 64, st, ix, o, (const int32_t*)U.ulist, (const int32_t*)J->count, A, J->count + 1, U.jlist, U.jkey, c->d_ctr);
     int cur = 1;
     for (int rounds = 0;; rounds += LH_EXT_LONG_GROUP) {
@@ -189,9 +216,7 @@ static int ext_long_queue(lh_context* c, const DOpts& o, hipStream_t st) {
         const int gs = (int)((n_jobs + 1023) / 1024 < 256 ? (n_jobs + 1023) / 1024 : 256);
         for (int u = 0; u < LH_EXT_LONG_GROUP; ++u) {
             const int other = cur ^ 3;
-            LH_LAUNCH(k_extj_count, gs, 256, st, (const int32_t*)(J->count + cur), (const int32_t*)U.jkey, J);
-            LH_LAUNCH(k_extj_offsets, 1, 256, st, J, cur, other);
-            LH_LAUNCH(k_extj_scatter, gs, 256, st, (const int32_t*)(J->count + cur), (const int32_t*)U.jkey, (const int32_t*)U.jlist, J, U.jorder);
+            ext_sort_jobs(st, gs, J, cur, other, U.jkey, U.jlist, U.jorder);
             LH_LAUNCH(k_ext_round<true>, 2560, 64, st, ix, o, (const int32_t*)(J->range + 2 * cur), J->next + cur, (const int32_t*)U.jorder, A, J->count + other, U.jlist, U.jkey,
                       J->count + 3, U.ulist, c->d_ctr);   // (a unit's verdict 2: its call is made by a whole wave, next; the unit list is free after round 0)
             LH_LAUNCH(k_ext_wround, gw, 64, st, ix, o, (const int32_t*)U.ulist, (const int32_t*)(J->count + 3), &J->wnext, A, J->count + other, U.jlist, U.jkey, c->d_ctr);
@@ -205,35 +230,27 @@ static int ext_long_queue(lh_context* c, const DOpts& o, hipStream_t st) {
             fprintf(stderr, "[lh] K4 long queue: %d reads as %d chain units, %d reads left to k_extend before and %d after the rounds; (still queued: %d, more than %d regions: %d, a seed inside an earlier chain's region: %d); jobs: narrow %d + %d, live-interval %d + %d, short full-band %d + %d\n",
                     hj.wave_range[1], hj.count[0], hj.heavy_range[1], hj.defer_range[1], hj.kinds[0], LH_EXT_MERGE_CAP, hj.kinds[1], hj.kinds[2], hj.kinds[3], hj.kinds[6], hj.kinds[4], hj.kinds[7], hj.kinds[5], hj.kinds[8]);
     }
-    LH_LAUNCH(k_extend, gw, 64, st, ix, o, N, (const int32_t*)Q.defer, (const int32_t*)J->defer_range, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains,
-              c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, 0);
+    launch_extend(c, o, st, Q.defer, J->defer_range, 0);
     return LH_OK;
 }
 
 static int stage2_run(lh_context* c, const DOpts& o, int& t) {
-    int N = c->n_reads;
+    int N = c->b.n_reads;
     const DIndex& ix = c->idx->d;
     c->ran_inference = false;
     if (c->flags & LH_F_EXT_WAVE) {   // wave-per-read extension (k_extend.h), kept for A/B measurements
         T_BEGIN("k_extend");
-        LH_LAUNCH(k_extend, N, 64, c->stream, ix, o, N, (const int32_t*)nullptr, (const int32_t*)nullptr, c->d_seq, c->q4, c->d_seq_off, c->d_seed_off, c->d_chains, c->d_cseeds,
-                  c->d_n_chains, c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, 1);
+        launch_extend(c, o, c->stream, nullptr, nullptr, 1);
         T_END();
     } else {   // a read's control flow on one lane (round 0 ran at the end of k_chain_lane), its DPs in rounds of sorted jobs (k_extend2.h)
         if ((i64)LH_MAXLEN * o.a + (o.pen_clip5 > o.pen_clip3 ? o.pen_clip5 : o.pen_clip3) >= 8192)
             return set_err(LH_E_LIMIT, "match score too large for the packed DP cells of the lane DP (need 250*a + clip bonus < 8192)");
         const int gl = (N + 63) / 64;
         const int gs = (N + 1023) / 1024 < 256 ? (N + 1023) / 1024 : 256, glr = gl < 2560 ? gl : 2560;   // persistent / grid-stride kernels (16 KB of LDS per wave: 10 waves per CU): a round without jobs costs a few microseconds
-        const int gw = N < 16384 ? N : 16384;
         bool long_q = true;
         const bool serial = (c->flags & LH_F_EXT_SERIAL) != 0;   // per-round timings: the wave-chained reads first, on the same stream
         ExtArgs A = ext_args(c);
-#define LH_EXT_WAVE(st_, rg_, lst, cnt_)                                                                                                                 \
-        LH_LAUNCH(k_extend, gw, 64, st_, ix, o, N, (const int32_t*)(lst), (const int32_t*)(rg_), c->d_seq, c->q4, c->d_seq_off,                          \
-                  c->d_seed_off, c->d_chains, c->d_cseeds, c->d_n_chains, c->d_srt, c->d_ord, c->d_reg_off, c->d_regs, c->d_n_regs, c->d_ctr, cnt_)
-#define LH_EXT_ROUND(k_, ncnt_, nlist_, nkey_)                                                                                                           \
-        LH_LAUNCH(k_ext_round<false>, glr, 64, c->stream, ix, o, (const int32_t*)(c->d_ext_jobs->range + 2 * (k_)), c->d_ext_jobs->next + (k_), (const int32_t*)c->d_ext_jorder, A, \
-                  ncnt_, nlist_, nkey_, c->d_ext_jobs->defer_range + 1, c->d_ext_defer, c->d_ctr)
+        DExtJobs* const J = c->d_ext_jobs;
         // reads with many seeds or chains (chained by the wave kernel): extended by the wave-per-read kernel (parallel over seeds and
         // columns), beside the rounds of the others (disjoint reads; ONE auxiliary stream: with more, two contexts of a process exceed
         // the hardware queues and serialise each other)
@@ -242,7 +259,7 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
             { int rc = ext_long_queue(c, o, c->stream); if (rc) return rc; }
             T_END();
             T_BEGIN("k_extend(heavy)");
-            LH_EXT_WAVE(c->stream, c->d_ext_jobs->heavy_range, c->d_ext_heavy, 0);   // a long side behind an indel or many mismatches (round 0's verdict)
+            launch_extend(c, o, c->stream, c->d_ext_heavy, J->heavy_range, 0);   // a long side behind an indel or many mismatches (round 0's verdict)
             T_END();
         } else {
             T_BEGIN("k_extend(rounds)");
@@ -253,17 +270,17 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
             // kernel at once; otherwise the long queue, after the rounds have been queued (the host looks at its length as it goes)
             const i64 hint = c->ext_hint_valid ? c->h_peek->prev_wave_reads : -1;
             long_q = !(hint >= 0 && hint < ext_long_min(N));
-            if (!long_q) LH_EXT_WAVE(c->aux[0], c->d_ext_jobs->wave_range, c->d_aln_r, 1);
-            LH_EXT_WAVE(c->aux[0], c->d_ext_jobs->heavy_range, c->d_ext_heavy, 0);   // a long side behind an indel or many mismatches (round 0's verdict)
+            if (!long_q) launch_extend(c, o, c->aux[0], c->d_aln_r, J->wave_range, 1);
+            launch_extend(c, o, c->aux[0], c->d_ext_heavy, J->heavy_range, 0);   // a long side behind an indel or many mismatches (round 0's verdict)
         }
         static const char* const round_names[8] = {"k_ext_round 1", "k_ext_round 2", "k_ext_round 3", "k_ext_round 4", "k_ext_round 5", "k_ext_round 6", "k_ext_round 7", "k_ext_round 8"};
         for (int k = 1; k <= LH_EXT_ROUNDS; ++k) {
             if (serial) T_BEGIN(round_names[k - 1 < 8 ? k - 1 : 7]);
-            LH_LAUNCH(k_extj_count, gs, 256, c->stream, (const int32_t*)(c->d_ext_jobs->count + k), (const int32_t*)c->d_ext_jkey, c->d_ext_jobs);
-            LH_LAUNCH(k_extj_offsets, 1, 256, c->stream, c->d_ext_jobs, k, -1);
-            LH_LAUNCH(k_extj_scatter, gs, 256, c->stream, (const int32_t*)(c->d_ext_jobs->count + k), (const int32_t*)c->d_ext_jkey, (const int32_t*)c->d_ext_jlist, c->d_ext_jobs, c->d_ext_jorder);
-            if (k < LH_EXT_ROUNDS) LH_EXT_ROUND(k, c->d_ext_jobs->count + k + 1, c->d_ext_jlist, c->d_ext_jkey);
-            else LH_EXT_ROUND(k, c->d_ext_jobs->defer_range + 1, c->d_ext_defer, (int32_t*)nullptr);   // what still needs a DP after the last round: the wave kernel
+            ext_sort_jobs(c->stream, gs, J, k, -1, c->d_ext_jkey, c->d_ext_jlist, c->d_ext_jorder);
+            // the round queues what needs a further DP for the next one; after the last round that is the wave kernel's list
+            const bool last = k == LH_EXT_ROUNDS;
+            LH_LAUNCH(k_ext_round<false>, glr, 64, c->stream, ix, o, (const int32_t*)(J->range + 2 * k), J->next + k, (const int32_t*)c->d_ext_jorder, A, last ? J->defer_range + 1 : J->count + k + 1,
+                      last ? c->d_ext_defer : c->d_ext_jlist, last ? (int32_t*)nullptr : c->d_ext_jkey, J->defer_range + 1, c->d_ext_defer, c->d_ctr);
             if (serial) T_END();
         }
         if (!serial) {
@@ -275,9 +292,7 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
             T_END();
         }
         T_BEGIN("k_extend(deferred)");
-        LH_EXT_WAVE(c->stream, c->d_ext_jobs->defer_range, c->d_ext_defer, 0);   // reads the rounds left to the wave kernel (their chains were counted by k_chain_lane)
-#undef LH_EXT_WAVE
-#undef LH_EXT_ROUND
+        launch_extend(c, o, c->stream, c->d_ext_defer, J->defer_range, 0);   // reads the rounds left to the wave kernel (their chains were counted by k_chain_lane)
         T_END();
     }
     if (lh_debug_sync()) {   // development aid: sanity of k_extend's output before the order-dependent stages
@@ -299,7 +314,7 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
     T_BEGIN("k_dedup");
     HIPCHK(hipMemsetAsync(&c->d_aln_count->flat, 0, sizeof(int32_t), c->stream));   // the list buffers are shared with K6 and K7, which run later
     LH_LAUNCH(k_dedup_fast, (N + 255) / 256, 256, c->stream, ix, o, N, (const i64*)c->d_reg_off, c->d_regs, c->d_n_regs, c->d_best, c->d_aln_r, &c->d_aln_count->flat, c->d_reg_clean);
-    LH_LAUNCH(k_dedup, N < 16384 ? N : 16384, 64, c->stream, ix, o, N, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_regs_tmp, c->d_ia, c->d_n_regs, c->d_best, c->d_ctr,
+    LH_LAUNCH(k_dedup, N < 16384 ? N : 16384, 64, c->stream, ix, o, N, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_regs_tmp, c->d_ia, c->d_n_regs, c->d_best, c->d_ctr,
               (const int32_t*)c->d_aln_r, (const int32_t*)&c->d_aln_count->flat, c->d_reg_clean);
     T_END();
     if (c->dump_stop_after_dedup) return LH_OK;
@@ -326,9 +341,9 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
     HIPCHK(hipMemsetAsync(c->R.mm_xctr, 0, sizeof(int32_t), c->stream));
     {   // (K5's and K6's per-read best scores are dead by now: d_best holds K7's; the read of every candidate slot goes where K8 will write the same numbers)
         const i64 n_cand = total < c->cand_cap ? total : c->cand_cap;
-        LH_LAUNCH(k_aln_prep, (N + 255) / 256, 256, c->stream, o, N, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_status, c->d_best, c->S.cand_read);
+        LH_LAUNCH(k_aln_prep, (N + 255) / 256, 256, c->stream, o, N, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_status, c->d_best, c->S.cand_read);
         if (n_cand > 0)
-            LH_LAUNCH(k_aln_flat, (int)((n_cand + 255) / 256), 256, c->stream, ix, o, n_cand, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, c->d_aln_r, c->d_aln_ci,
+            LH_LAUNCH(k_aln_flat, (int)((n_cand + 255) / 256), 256, c->stream, ix, o, n_cand, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, c->d_aln_r, c->d_aln_ci,
                       &c->d_aln_count->flat, c->d_ctr, c->q4, (const int32_t*)c->d_best, (const int32_t*)c->S.cand_read);
     }
     const int g7 = N < c->grid_aln ? N : c->grid_aln;
@@ -337,14 +352,14 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
     const RegsTmpLists T7(c->d_regs_tmp, (size_t)c->regpool_cap);   // (K5's and K6's region scratch is dead by now: the lists of the candidates K7's kernels hand on)
     AlnCounts* const n7 = c->d_aln_count;
     // (r06) equal spans and five or six mismatches: a second, longer look without the DP (aln_deep_check) at what k_aln_flat listed
-    LH_LAUNCH(k_aln_flat2, g7 < 2048 ? g7 : 2048, 256, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci,
+    LH_LAUNCH(k_aln_flat2, g7 < 2048 ? g7 : 2048, 256, c->stream, ix, o, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci,
               (const int32_t*)&n7->flat, T7.deep_r, T7.deep_ci, &n7->grp16, c->d_ctr, c->q4, (const int32_t*)c->d_best);
-    LH_LAUNCH(k_aln_grp<16>, g7, 64, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)T7.deep_r,
+    LH_LAUNCH(k_aln_grp<16>, g7, 64, c->stream, ix, o, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)T7.deep_r,
               (const int32_t*)T7.deep_ci, (const int32_t*)&n7->grp16, T7.wide_r, T7.wide_ci, &n7->grp32);
     // (r05) what four-per-wave in a band of 7 could not settle: two per wave in a band of 15; the first kernel's input list is free by now and takes what is still left for k_aln
-    LH_LAUNCH(k_aln_grp<32>, g7, 64, c->stream, ix, o, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)T7.wide_r,
+    LH_LAUNCH(k_aln_grp<32>, g7, 64, c->stream, ix, o, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->d_status, c->d_ctr, (const int32_t*)T7.wide_r,
               (const int32_t*)T7.wide_ci, (const int32_t*)&n7->grp32, c->d_aln_r, c->d_aln_ci, &n7->full);
-    LH_LAUNCH(k_aln, g7, 64, c->stream, ix, o, N, c->d_seq, c->d_seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_zpool, c->d_status, c->d_ctr,
+    LH_LAUNCH(k_aln, g7, 64, c->stream, ix, o, N, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_zpool, c->d_status, c->d_ctr,
               (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci, (const int32_t*)&n7->full);
     T_END();
     if (o.run_inference) { int rc = rfa_run(c, o, t); if (rc) return rc; }
@@ -352,7 +367,7 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
 }
 
 static int stage2_dump_regs(lh_context* c, DumpArenaH* A) {
-    int N = c->n_reads;
+    int N = c->b.n_reads;
     std::vector<i64> reg_off;
     std::vector<int32_t> n_regs;
     std::vector<DReg> regs;
@@ -419,7 +434,7 @@ static int pipe_download_begin(lh_context* c) {
         return LH_OK;
     }
     HIPCHK(hipSetDevice(c->idx->device));
-    const int N = c->n_reads;
+    const int N = c->b.n_reads;
     // three small read-backs first: the OR of the status words, the candidate total, the packed CIGAR / mismatch totals
     int32_t* const status_or = &c->d_aln_count->flat;   // (K7's counter: free by now)
     HIPCHK(hipMemsetAsync(status_or, 0, sizeof(int32_t), c->stream));
@@ -644,91 +659,97 @@ static int rfa_tier_slabs(lh_context* c, int k, i64 listed, bool a_slab_each = f
     return LH_OK;
 }
 
+// The slabs a launch of k_rfa (post: of k_rfa_post) runs on, with that launch's work counter.  The regular slabs take a wave per barcode up to grid_rfa; a barcode
+// that does not fit a tier's slab is listed for the next — the middle tiers 0 and 1, then the few large slabs of the last one: fewer waves, larger slabs
+enum { RFA_REGULAR = -1, RFA_LAST = 2 };
+static RfaTier rfa_tier(const lh_context* c, int k, bool post) {
+    RfaCounters* const n = c->d_bc_next;
+    if (k == RFA_REGULAR) return {c->d_slab, c->slab_bytes, c->b.n_bc < c->grid_rfa ? c->b.n_bc : c->grid_rfa, post ? &n->post_next : &n->next};
+    if (k == RFA_LAST) return {c->d_slab2, c->slab2_bytes, c->grid_rfa2, post ? &n->post_last_next : &n->last_next};
+    return {c->d_slab_mid[k], c->slab_mid_bytes[k], c->grid_rfa_mid[k], post ? &n->tier[k].post_next : &n->tier[k].next};
+}
+static void launch_rfa(lh_context* c, const DOpts& o, const RfaTier& T, hipStream_t st, RfaList in, RfaList out) {
+    LH_LAUNCH(k_rfa, T.grid, 64, st, c->idx->d, o, c->b.n_bc, c->b.bc_pair_off, c->b.bc_do_rfa, c->b.name_seed, c->b.cen_start, c->b.cen_end, c->R, c->S, c->cand_cap, T.slab, T.bytes,
+              c->d_status, T.next, (const int32_t*)in.list, (const int32_t*)in.count, out.list, out.count, c->d_rfa_hr, &c->d_bc_next->heavy_reads, c->d_bc_lmp);
+}
+static void launch_rfa_post(lh_context* c, const DOpts& o, const RfaTier& T, hipStream_t st, RfaList in, RfaList out) {
+    LH_LAUNCH(k_rfa_post, T.grid, 64, st, c->idx->d, o, c->b.n_bc, c->b.bc_pair_off, (const i64*)c->b.cen_start, (const i64*)c->b.cen_end, c->R, c->S, c->cand_cap, T.slab, T.bytes,
+              c->d_status, T.next, (const int32_t*)in.list, (const int32_t*)in.count, out.list, out.count);
+}
+// The `listed` barcodes a launch turned away (in), through the middle tiers from k_first on and then the last slabs: only the last one's verdict is final.  (r06) The
+// host looks at a list's length before it launches the tier that takes it (one small read-back; nothing is launched for an empty list — the usual batch) and makes
+// sure the tier has slabs (rfa_tier_slabs)
+static int rfa_cascade(lh_context* c, const DOpts& o, bool post, RfaList in, i64 listed, int k_first) {
+    const RfaOvfMid mid(c->d_rfa_ovf_mid, (size_t)c->cap_bc);
+    const auto launch = post ? launch_rfa_post : launch_rfa;
+    for (int k = k_first; k < 2 && listed > 0; ++k) {
+        if (!c->slab_mid_bytes[k]) continue;
+        { int rc = rfa_tier_slabs(c, k, listed); if (rc) return rc; }
+        RfaCounters::Tier* const n = &c->d_bc_next->tier[k];
+        const RfaList out{post ? mid.post[k] : mid.rfa[k], post ? &n->post_n_ovf : &n->n_ovf};
+        launch(c, o, rfa_tier(c, k, post), c->stream, in, out);
+        in = out;
+        { int rc = rfa_list_len(c, in.count, &listed); if (rc) return rc; }
+    }
+    if (listed > 0) launch(c, o, rfa_tier(c, RFA_LAST, post), c->stream, in, RfaList{nullptr, nullptr});
+    return LH_OK;
+}
+
 static int rfa_run(lh_context* c, const DOpts& o, int& t) {
     RfaCounters* const ctr = c->d_bc_next;
     HIPCHK(hipMemsetAsync(ctr, 0, sizeof(RfaCounters), c->stream));
     T_BEGIN("k_rfa");
-    const int N = c->n_reads, P = c->n_pairs;
+    const int N = c->b.n_reads, P = c->b.n_pairs;
     // the wave kernels' scratch: the barcode program's slabs while they fit a pair's lists and Go's generator state (a context made with tiny slabs: the large ones)
     const bool small_ok = c->slab_bytes >= ((i64)1 << 20);
     uint8_t* const wslab = small_ok ? c->d_slab : c->d_slab2;
     const i64 wslab_bytes = small_ok ? c->slab_bytes : c->slab2_bytes;
     const int wgrid = small_ok ? c->grid_rfa : c->grid_rfa2;
     LH_LAUNCH(k_rfa_init, 4096, 256, c->stream, N, c->R, c->S, c->cand_cap);
-    LH_LAUNCH(k_rfa_tag, (P + 255) / 256, 256, c->stream, o, P, (const u64*)c->d_name_seed, c->R, c->S, c->cand_cap, c->d_rfa_hp, &ctr->heavy_pairs);
-    LH_LAUNCH(k_rfa_tag_w, wgrid, 64, c->stream, o, (const u64*)c->d_name_seed, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hp, (const int32_t*)&ctr->heavy_pairs, c->d_status);
-    int g = c->n_bc < c->grid_rfa ? c->n_bc : c->grid_rfa;
-    // a barcode that does not fit a tier's slab is listed for the next: fewer waves, larger slabs; only the last one's verdict is final.  (r06) The host looks at a list's
-    // length before it launches the tier that takes it (one small read-back; nothing is launched for an empty list — the usual batch) and makes sure the tier has slabs
-    // (rfa_tier_slabs).
+    LH_LAUNCH(k_rfa_tag, (P + 255) / 256, 256, c->stream, o, P, (const u64*)c->b.name_seed, c->R, c->S, c->cand_cap, c->d_rfa_hp, &ctr->heavy_pairs);
+    LH_LAUNCH(k_rfa_tag_w, wgrid, 64, c->stream, o, (const u64*)c->b.name_seed, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hp, (const int32_t*)&ctr->heavy_pairs, c->d_status);
     // (r06) most candidates first; the barcodes whose tables cannot fit a regular slab apart (k_rfa_order)
     const RfaOrder ord(c->d_rfa_order, (size_t)c->cap_bc);
-    const RfaOvfMid ovf_mid(c->d_rfa_ovf_mid, (size_t)c->cap_bc);
-    LH_LAUNCH(k_rfa_order, 1, 256, c->stream, c->n_bc, (const int32_t*)c->d_bc_pair_off, c->R, ord.all, ord.big, ord.rest, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
+    const RfaList all{ord.all, ord.n_all}, big{ord.big, ord.n_big}, rest{ord.rest, ord.n_rest};
+    LH_LAUNCH(k_rfa_order, 1, 256, c->stream, c->b.n_bc, (const int32_t*)c->b.bc_pair_off, c->R, ord.all, ord.big, ord.rest, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
     {
         // the first tier has slabs (an earlier batch needed them): the barcodes that cannot fit a regular slab start there at once, on a second stream, beside the first launch;
         // what they leave goes to the list the tier's own launch leaves its overflow in.  No slabs yet: the first launch sees every barcode and turns those away, as before
         const bool pre = c->slab_mid_bytes[0] && c->d_slab_mid[0] && c->grid_rfa_mid[0] > 0;
-        const int32_t *wl = pre ? ord.rest : ord.all, *wc = pre ? ord.n_rest : ord.n_all;
-        int32_t *ol = c->d_rfa_ovf, *oc = &ctr->n_ovf;
+        RfaList ovf{c->d_rfa_ovf, &ctr->n_ovf};
+        const RfaList routed_ovf{RfaOvfMid(c->d_rfa_ovf_mid, (size_t)c->cap_bc).rfa[0], &ctr->tier[0].n_ovf};
         if (pre) {
             HIPCHK(hipEventRecord(c->ev_fork, c->stream));
             HIPCHK(hipStreamWaitEvent(c->aux[0], c->ev_fork, 0));
-            LH_LAUNCH(k_rfa, c->grid_rfa_mid[0], 64, c->aux[0], c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab_mid[0], c->slab_mid_bytes[0], c->d_status, &ctr->routed_next, (const int32_t*)ord.big, (const int32_t*)ord.n_big,
-                      ovf_mid.rfa[0], &ctr->tier[0].n_ovf, c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
+            RfaTier routed = rfa_tier(c, 0, false);
+            routed.next = &ctr->routed_next;
+            launch_rfa(c, o, routed, c->aux[0], big, routed_ovf);
             HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
         }
-        LH_LAUNCH(k_rfa, g, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap, c->d_slab,
-                  c->slab_bytes, c->d_status, &ctr->next, wl, wc, ol, oc, c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
+        launch_rfa(c, o, rfa_tier(c, RFA_REGULAR, false), c->stream, pre ? rest : all, ovf);
         if (pre) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
         i64 listed = 0;
         LH_LAUNCH(k_peek_i32, 1, 1, c->stream, (const int32_t*)ord.n_big, &c->h_peek->rfa_routed);   // (read with the list's length below: one synchronisation)
-        { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
+        { int rc = rfa_list_len(c, ovf.count, &listed); if (rc) return rc; }
         const i64 n_routed = c->h_peek->rfa_routed;
         int k_first = 0;
         if (pre && listed == 0) {   // nothing for the first tier's own launch: what the routed barcodes left there is the next tier's list
-            ol = ovf_mid.rfa[0]; oc = &ctr->tier[0].n_ovf;
-            { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
+            ovf = routed_ovf;
+            { int rc = rfa_list_len(c, ovf.count, &listed); if (rc) return rc; }
             k_first = 1;
         }
-        for (int k = k_first; k < 2 && listed > 0; ++k) {
-            if (!c->slab_mid_bytes[k]) continue;
-            { int rc = rfa_tier_slabs(c, k, listed); if (rc) return rc; }
-            wl = ol; wc = oc;
-            ol = ovf_mid.rfa[k]; oc = &ctr->tier[k].n_ovf;
-            LH_LAUNCH(k_rfa, c->grid_rfa_mid[k], 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab_mid[k], c->slab_mid_bytes[k], c->d_status, &ctr->tier[k].next, wl, wc, ol, oc, c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
-            { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
-        }
-        if (listed > 0)
-            LH_LAUNCH(k_rfa, c->grid_rfa2, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, c->d_bc_do_rfa, c->d_name_seed, c->d_cen_start, c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab2, c->slab2_bytes, c->d_status, &ctr->last_next, (const int32_t*)ol, (const int32_t*)oc, (int32_t*)nullptr, (int32_t*)nullptr,
-                      c->d_rfa_hr, &ctr->heavy_reads, c->d_bc_lmp);
+        { int rc = rfa_cascade(c, o, false, ovf, listed, k_first); if (rc) return rc; }
         // the next batch's routed barcodes each want a slab of the first tier: as many as this batch routed (the tier grows when that is more than twice what it has)
         if (c->slab_mid_bytes[0] && n_routed > 0) { int rc = rfa_tier_slabs(c, 0, n_routed, true); if (rc) return rc; }
     }
-    LH_LAUNCH(k_rfa_mq_w, wgrid, 64, c->stream, o, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hr,
+    LH_LAUNCH(k_rfa_mq_w, wgrid, 64, c->stream, o, (const i64*)c->b.cen_start, (const i64*)c->b.cen_end, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hr,
               (const int32_t*)&ctr->heavy_reads, (const double*)c->d_bc_lmp, c->d_status);
     {
-        const int32_t *wl = ord.all, *wc = ord.n_all;
-        int32_t *ol = c->d_rfa_ovf2, *oc = &ctr->post_n_ovf;
-        LH_LAUNCH(k_rfa_post, g, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, c->cand_cap, c->d_slab, c->slab_bytes,
-                  c->d_status, &ctr->post_next, wl, wc, ol, oc);
+        const RfaList ovf{c->d_rfa_ovf2, &ctr->post_n_ovf};
+        launch_rfa_post(c, o, rfa_tier(c, RFA_REGULAR, true), c->stream, all, ovf);
         i64 listed = 0;
-        { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
-        for (int k = 0; k < 2 && listed > 0; ++k) {
-            if (!c->slab_mid_bytes[k]) continue;
-            { int rc = rfa_tier_slabs(c, k, listed); if (rc) return rc; }
-            wl = ol; wc = oc;
-            ol = ovf_mid.post[k]; oc = &ctr->tier[k].post_n_ovf;
-            LH_LAUNCH(k_rfa_post, c->grid_rfa_mid[k], 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, c->cand_cap,
-                      c->d_slab_mid[k], c->slab_mid_bytes[k], c->d_status, &ctr->tier[k].post_next, wl, wc, ol, oc);
-            { int rc = rfa_list_len(c, oc, &listed); if (rc) return rc; }
-        }
-        if (listed > 0)
-            LH_LAUNCH(k_rfa_post, c->grid_rfa2, 64, c->stream, c->idx->d, o, c->n_bc, c->d_bc_pair_off, (const i64*)c->d_cen_start, (const i64*)c->d_cen_end, c->R, c->S, c->cand_cap, c->d_slab2,
-                      c->slab2_bytes, c->d_status, &ctr->post_last_next, (const int32_t*)ol, (const int32_t*)oc, (int32_t*)nullptr, (int32_t*)nullptr);
+        { int rc = rfa_list_len(c, ovf.count, &listed); if (rc) return rc; }
+        { int rc = rfa_cascade(c, o, true, ovf, listed, 0); if (rc) return rc; }
     }
     T_END();
 #ifdef LH_RFA_PROF
@@ -1001,22 +1022,10 @@ int lh_diag_rescue_sw(int device, int32_t n_cases, const int32_t* q_off, const u
     HIPCHK(tmp.alloc(&d_ctr, sizeof(DCounters) * LH_CTR_SLOTS)); HIPCHK(tmp.alloc(&d_keys, sizeof(int32_t) * 3 * LH_RC_KEYS)); HIPCHK(tmp.alloc(&d_ord, ocap * 4)); HIPCHK(tmp.alloc(&d_ord2, ocap * 4));
     HIPCHK(hipMemcpy(d_mate, mate.data(), mate.size(), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_pac, pac.data(), pac.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_jobs, jobs.data(), sizeof(RJob) * (size_t)n_cases, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_meta, 0, sizeof(RMeta))); HIPCHK(hipMemset(d_ctr, 0, sizeof(DCounters) * LH_CTR_SLOTS)); HIPCHK(hipMemset(d_keys, 0, sizeof(int32_t) * 3 * LH_RC_KEYS));
-    HIPCHK(hipMemset(d_ord, 0xff, ocap * 4)); HIPCHK(hipMemset(d_ord2, 0xff, ocap * 4));
+    HIPCHK(hipMemset(d_meta, 0, sizeof(RMeta))); HIPCHK(hipMemset(d_ctr, 0, sizeof(DCounters) * LH_CTR_SLOTS));
     ix.pac = d_pac; ix.l_pac = (i64)nt;
-    hipStream_t st = nullptr;
-    const i64 total = n_cases;
-    const int gb = (int)((total + 4095) / 4096);
-    // the launches of rescue_dir after the emitting pass, one after the other
-    if (!full) LH_LAUNCH(k_resc_cert, (int)((total + 3) / 4 < 4096 ? (total + 3) / 4 : 4096), 64, st, ix, o, total, d_jobs, (const uint8_t*)d_mate, (int)weaken);
-    LH_LAUNCH((k_resc_bucket1<false>), gb, 256, st, total, (const RJob*)d_jobs, d_keys, d_keys + 2 * LH_RC_KEYS, (const int32_t*)(d_keys + LH_RC_KEYS), d_ord, d_ctr);
-    LH_LAUNCH(k_resc_offsets1, 1, 1, st, d_meta, (const int32_t*)d_keys, d_keys + LH_RC_KEYS, d_keys + 2 * LH_RC_KEYS, (i64*)nullptr);
-    LH_LAUNCH((k_resc_bucket1<true>), gb, 256, st, total, (const RJob*)d_jobs, d_keys, d_keys + 2 * LH_RC_KEYS, (const int32_t*)(d_keys + LH_RC_KEYS), d_ord, d_ctr);
-    LH_LAUNCH((k_resc_sw<false>), (int)(ocap / 8), 64, st, ix, o, d_jobs, (const int32_t*)d_ord, (const uint8_t*)d_mate, d_meta);
-    LH_LAUNCH((k_resc_bucket2<false>), gb, 256, st, total, (const RJob*)d_jobs, o.min_seed_len * o.a, d_meta, d_ord2);
-    LH_LAUNCH(k_resc_offsets, 1, 1, st, d_meta, 1, (i64*)nullptr, (const i64*)nullptr);
-    LH_LAUNCH((k_resc_bucket2<true>), gb, 256, st, total, (const RJob*)d_jobs, o.min_seed_len * o.a, d_meta, d_ord2);
-    LH_LAUNCH((k_resc_sw<true>), (int)(ocap / 8), 64, st, ix, o, d_jobs, (const int32_t*)d_ord2, (const uint8_t*)d_mate, d_meta);
+    // what rescue_dir runs after its emitting pass, on jobs made here (no order by striping exists yet: both order arrays are whole and padded alike)
+    { int rc = rescue_sw((hipStream_t)0, ix, o, n_cases, d_jobs, d_mate, d_meta, d_keys, d_ord, (i64)ocap, d_ord2, (i64)ocap, d_ctr, full != 0, (int)weaken); if (rc) return rc; }
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(jobs.data(), d_jobs, sizeof(RJob) * (size_t)n_cases, hipMemcpyDeviceToHost));

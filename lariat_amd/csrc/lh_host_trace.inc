@@ -143,11 +143,11 @@ static int prof_rfa(lh_context* c) {
     HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(lh_rfa_prof), sizeof h));
     unsigned long long tot = 0;
     for (int i = 0; i < 24; ++i) tot += h[i];
-    fprintf(stderr, "[lh] k_rfa phases (shader clocks summed over waves, %d barcodes):\n", c->n_bc);
-    for (int i = 0; i < 15; ++i) fprintf(stderr, "[lh]   %-44s %6.2f %%  %10.1f k clocks per barcode\n", names[i], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, (double)h[i] / 1e3 / (c->n_bc ? c->n_bc : 1));
+    fprintf(stderr, "[lh] k_rfa phases (shader clocks summed over waves, %d barcodes):\n", c->b.n_bc);
+    for (int i = 0; i < 15; ++i) fprintf(stderr, "[lh]   %-44s %6.2f %%  %10.1f k clocks per barcode\n", names[i], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, (double)h[i] / 1e3 / (c->b.n_bc ? c->b.n_bc : 1));
     {   // parts of the two phases above, when their markers are compiled in (their clocks are NOT in the phase's own line then)
         static const char* const sub[8] = {"  inferMolecules", "  step 1: staging a tile", "  step 1: the entries of a tile", "  sort: network", "  sort: tie check + copy", "  sort: Go's algorithm on ranks", "  sort: smallest position", "  sort: keys"};
-        for (int i = 16; i < 24; ++i) if (h[i]) fprintf(stderr, "[lh]   %-44s %6.2f %%  %10.1f k clocks per barcode\n", sub[i - 16], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, (double)h[i] / 1e3 / (c->n_bc ? c->n_bc : 1));
+        for (int i = 16; i < 24; ++i) if (h[i]) fprintf(stderr, "[lh]   %-44s %6.2f %%  %10.1f k clocks per barcode\n", sub[i - 16], tot ? 100.0 * (double)h[i] / (double)tot : 0.0, (double)h[i] / 1e3 / (c->b.n_bc ? c->b.n_bc : 1));
     }
     memset(h, 0, sizeof h);
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_rfa_prof), h, sizeof h));
@@ -177,12 +177,12 @@ static int hist_rfa(lh_context* c) {
     {
         RfaCounters bn;
         HIPCHK(hipMemcpy(&bn, c->d_bc_next, sizeof bn, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[lh] k_rfa tiers: %d barcodes; listed for the 16 MiB tier %d (of %d waves), for the 128 MiB tier %d (of %d), for the last launch %d; k_rfa_post: %d / %d / %d\n", c->n_bc, bn.n_ovf,
+        fprintf(stderr, "[lh] k_rfa tiers: %d barcodes; listed for the 16 MiB tier %d (of %d waves), for the 128 MiB tier %d (of %d), for the last launch %d; k_rfa_post: %d / %d / %d\n", c->b.n_bc, bn.n_ovf,
                 c->grid_rfa_mid[0], c->grid_rfa_mid[0] ? bn.tier[0].n_ovf : 0, c->grid_rfa_mid[1], c->grid_rfa_mid[1] ? bn.tier[1].n_ovf : (c->grid_rfa_mid[0] ? bn.tier[0].n_ovf : bn.n_ovf), bn.post_n_ovf,
                 bn.tier[0].post_n_ovf, bn.tier[1].post_n_ovf);
     }
     HIPCHK(hipMemcpyFromSymbol(hh, HIP_SYMBOL(lh_rfa_hist), sizeof hh));
-    fprintf(stderr, "[lh] k_rfa, time per barcode (longest %.3f ms, sum %.1f ms over %d barcodes):", (double)hh[32] / 1e5, (double)hh[33] / 1e5, c->n_bc);
+    fprintf(stderr, "[lh] k_rfa, time per barcode (longest %.3f ms, sum %.1f ms over %d barcodes):", (double)hh[32] / 1e5, (double)hh[33] / 1e5, c->b.n_bc);
     for (int b = 0; b < 32; ++b) if (hh[b]) fprintf(stderr, " <%.4g ms: %llu", (double)(2ull << b) / 1e5, hh[b]);
     {
         unsigned long long nb = 0;

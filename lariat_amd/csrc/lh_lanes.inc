@@ -157,7 +157,7 @@ int lh_last_rounds(lh_context* c, int32_t lane, lh_round_info* out) {
         HIPCHK(hipStreamSynchronize(p->stream));
         R.max_bc = p->plan.hdr()->max_barcode; R.max_bc_seeds = p->plan.hdr()->max_barcode_seeds;
         if (p->plan.hdr()->n_rounds != 1 || p->plan.hdr()->total_seeds != R.total_seeds) return set_err(LH_E_HIP, "lh_last_rounds: the plan of a batch that ran whole is inconsistent");
-        R.first_bc.assign({0, p->n_bc}); R.seeds.assign(1, R.total_seeds); R.need.assign(1, seed_need(p, R.total_seeds));
+        R.first_bc.assign({0, p->b.n_bc}); R.seeds.assign(1, R.total_seeds); R.need.assign(1, seed_need(p, R.total_seeds));
         R.have_max = true;
     }
     const int32_t b0 = lane && lanes_split(c) ? c->slot_cut[(size_t)c->cur_slot][(size_t)lane - 1] : 0;
@@ -168,6 +168,15 @@ int lh_last_rounds(lh_context* c, int32_t lane, lh_round_info* out) {
     return LH_OK;
 }
 
+// part behind acc (the first part becomes acc): merged into a new result, and both are freed whatever the outcome.  The rounds' parts and the lanes' fold this way
+static int merge_into(lh_result*& acc, lh_result* part) {
+    if (!acc) { acc = part; return LH_OK; }
+    lh_result* m = nullptr;
+    const int rc = merge_results(acc, part, &m);
+    lh_result_free(acc); lh_result_free(part);
+    acc = m;
+    return rc;
+}
 // b's arrays behind a's in one block, column by column as LH_RESULT_COLS says (lh_result_cols.h): candidate / CIGAR / mismatch indices of b shifted by a's totals
 static int merge_results(lh_result* a, lh_result* b, lh_result** out) {
     const size_t Ca = (size_t)a->n_cand, Cb = (size_t)b->n_cand;
@@ -254,13 +263,10 @@ int lh_result_download_end(lh_context* c, lh_result** out) {
         }
         first_read += rs[k]->n_reads;
     }
-    lh_result* acc = rs[0];
-    for (size_t k = 1; k <= M; ++k) {
-        lh_result* m = nullptr;
-        int rc = merge_results(acc, rs[k], &m);
-        lh_result_free(acc); lh_result_free(rs[k]);
+    lh_result* acc = nullptr;
+    for (size_t k = 0; k <= M; ++k) {
+        int rc = merge_into(acc, rs[k]);
         if (rc) { for (size_t q = k + 1; q <= M; ++q) lh_result_free(rs[q]); return rc; }
-        acc = m;
     }
     *out = acc;
     return LH_OK;

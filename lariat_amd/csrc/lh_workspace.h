@@ -33,6 +33,19 @@ struct DevGroup {
 };
 #define DALLOC(g, p, n) do { int rc_ = (g).alloc(p, (size_t)(n)); if (rc_) return rc_; } while (0)
 
+// ------------------------------------------------------------------------------------------------ a batch on the device
+// What the kernel sequence reads of its input: the arrays of lh_batch and their sizes.  One value: a slot holds one for its own buffers (lh_context::DevBatch), the
+// context holds the selected one (lh_context::b: a slot's, or a round's part of it, lh_host.inc: part_view), and whatever saves, restores or replaces the selection
+// copies all of it.  It owns nothing: the arrays belong to a slot's DevGroup or to the rounds' (RoundBufs)
+struct BatchView {
+    uint8_t* seq = nullptr; i64* seq_off = nullptr;   // the reads' bases, a byte each, and where each read begins [n_reads + 1]
+    u64* name_seed = nullptr;                         // per pair
+    int32_t* bc_pair_off = nullptr; uint8_t* bc_do_rfa = nullptr;   // per barcode: its first pair [n_bc + 1]; run the inference for it?
+    i64 *cen_start = nullptr, *cen_end = nullptr;     // per contig of the index: the centromere's interval (-1: none)
+    int n_pairs = 0, n_reads = 0, n_bc = 0; bool has_cen = false; i64 n_bases = 0;
+    int max_len = LH_MAXLEN;   // the longest read (K1 stages its queries in that many bases' worth of LDS)
+};
+
 // ------------------------------------------------------------------------------------------------ counter blocks (device)
 // K1's work counters: cleared as a whole when K1 starts, big_pass again before every second-chance round
 struct K1Counters {
@@ -174,3 +187,7 @@ struct RfaOvfMid {
     int32_t *rfa[2], *post[2];
     RfaOvfMid(int32_t* base, size_t cap_bc) : rfa{base, base + (cap_bc + 1)}, post{base + 2 * (cap_bc + 1), base + 3 * (cap_bc + 1)} {}
 };
+// what one launch of k_rfa / k_rfa_post runs on (lh_host_stage2.inc: rfa_tier): a wave per slab, the barcodes taken off a list one by one through a work counter
+struct RfaTier { uint8_t* slab; i64 bytes; int grid; int32_t* next; };
+// a barcode list on the device and its length: a launch's work list, or where it lists what it turns away (none: the last slabs' verdict is final)
+struct RfaList { int32_t *list, *count; };

@@ -225,6 +225,50 @@ def case_split_download(lib, oracle):
     assert_same_bytes(ctx.download(), u["R"])
 
 
+def case_second_slot_centromeres(lib, oracle):
+    """case 8: rounds on a batch that is not in slot 0 and that carries centromeres, between runs of another batch in slot 0: a part is the selected batch's (its
+    centromere arrays included), the selection is the whole batch's again afterwards, and the other slot is untouched.  Context A (default budget) runs both batches
+    whole, context B the same sequence within the budget of case 1"""
+    u = uneven(lib, oracle)
+    b = u["b"]
+    names, contigs = u["genome"]
+    cen_start, cen_end = np.array([0, -1], dtype=np.int64), np.array([len(contigs[0]), -1], dtype=np.int64)   # all of c0; c1 has none
+    b2 = capi.Batch.from_arrays(b.seq, b.seq_off, b.bc_pair_off, b.name_seed, bc_do_rfa=b.bc_do_rfa, cen_start=cen_start, cen_end=cen_end)
+    b0 = helpers.batch_of(helpers.small_reads(names, contigs, n_barcodes=4, pairs=40))   # half the capacity, on unique sequence: within context B's budget as a whole
+
+    def sequence(ctx):
+        ctx.upload_slot(0, b0)
+        ctx.upload_slot(1, b2)
+        out = []
+        for slot in (1, 0):
+            ctx.select(slot)
+            ctx.align_resident(lib.opts())
+            out += [ctx.download(), ctx.rounds()]
+        return out
+
+    Rc, whole1, R0, whole0 = sequence(u["idx"].context(CAP))
+    assert whole1["n_rounds"] == 1 and whole0["n_rounds"] == 1
+    assert Rc.n_cand == u["R"].n_cand and ((Rc.mapq == 0) & (u["R"].mapq != 0)).any() and (Rc.mapq != 0).any()   # a best hit inside the centromere; one outside
+    ctx = u["idx"].context(CAP, seed_budget_kb=budget_kb(u["info"]))
+    res1, info1, res0, info0 = sequence(ctx)
+    assert_plan(info1, b2.n_barcodes, at_least=3)
+    assert_same_bytes(res1, Rc)
+    helpers.assert_same_result(res1, u["oidx"].align_barcodes(b2, threads=8), inference=True)
+    print("slot 0:", {k: info0[k] for k in ("n_rounds", "need_bytes", "budget_bytes")})
+    assert info0["n_rounds"] == 1 and info0["need_bytes"] <= info0["budget_bytes"], info0
+    assert_same_bytes(res0, R0)
+    # the selection after a run in rounds is the whole batch's, not the last part's: the stage dump is one pass over every read of it (or, over budget, none)
+    ctx.select(1)
+    ctx.align_resident(lib.opts())
+    assert ctx.rounds()["n_rounds"] >= 3
+    with pytest.raises(capi.LhError) as e:
+        ctx.stage_dump()
+    assert e.value.code == capi.LH_E_CAPACITY and ("the batch has %d seeds" % u["seeds"].sum()) in str(e.value), str(e.value)
+    ctx.select(0)
+    assert ctx.stage_dump().n_reads == 2 * b0.n_pairs
+    return info1, info0
+
+
 @pytest.fixture(scope="module")
 def emu_libs():
     subprocess.check_call(["make", "-s", "-C", EMU_DIR])
@@ -260,3 +304,8 @@ def test_emu_rounds_lanes(emu_libs, oracle, build):
 @pytest.mark.parametrize("build", sorted(BUILDS))
 def test_emu_rounds_split_download(emu_libs, oracle, build):
     case_split_download(emu_libs[build], oracle)
+
+
+@pytest.mark.parametrize("build", sorted(BUILDS))
+def test_emu_rounds_second_slot_centromeres(emu_libs, oracle, build):
+    print(build, case_second_slot_centromeres(emu_libs[build], oracle))

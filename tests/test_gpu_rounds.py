@@ -39,6 +39,10 @@ def test_rounds_split_download(lib, oracle):
     cases.case_split_download(lib, oracle)
 
 
+def test_rounds_second_slot_centromeres(lib, oracle):
+    print(cases.case_second_slot_centromeres(lib, oracle))
+
+
 @pytest.mark.parametrize("flags", [capi.LH_F_CHAIN_WAVE, capi.LH_F_EXT_WAVE, capi.LH_F_RESCUE_FULL])
 def test_rounds_flags(lib, oracle, flags):
     cases.case_uneven_barcodes(lib, oracle, flags=flags)
