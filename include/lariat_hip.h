@@ -490,7 +490,7 @@ int lh_bam_open(const char* dir, int32_t n_contigs, const char* const* contig_na
                 int32_t position_chunk_size, int32_t first_chunk, const char* command_line, int32_t threads, lh_bam_writer** out);
 /* appends the records of one batch (lh_records_text order) to bc_sorted_bam.bam and to their position bucket */
 int lh_bam_append(lh_bam_writer* w, const lh_result* res, const lh_ingest_batch* in);
-int lh_bam_set_level(lh_bam_writer* w, int32_t level);  /* zlib level of the BGZF blocks written from now on: -1 (default) .. 9 */
+int lh_bam_set_level(lh_bam_writer* w, int32_t level);  /* zlib level of the BGZF blocks written from now on: -1 (default) .. 9 (host path only: see lh_bam_set_device) */
 int lh_bam_timings(const lh_bam_writer* w, double* records_s, double* join_s, double* write_s);  /* the last lh_bam_append's phases */
 int lh_bam_set_flags(lh_bam_writer* w, int32_t flags); /* LH_REC_* for the records appended from now on (CreateBAMs' debugTags, bamwriter.go:133) */
 int lh_bam_close(lh_bam_writer* w); /* flushes, writes the BGZF end-of-file blocks, frees w */
@@ -499,6 +499,25 @@ int lh_bam_close(lh_bam_writer* w); /* flushes, writes the BGZF end-of-file bloc
  * bc_sorted_bam.bam that is the single-process file (input order), for a position bucket the same multiset of records.
  * BGZF blocks are copied as they are; later shards lose their header, every end-of-file block but the last is dropped. */
 int lh_bam_concat(int32_t n_shards, const char* const* shard_dirs, const char* out_dir);
+
+/* BGZF on the device.  An lh_bgzf is a device compressor: an object of its own beside the contexts (a writer thread may use it while another thread aligns), with
+ * two buffer sets (a low-priority stream, pinned staging and device buffers for max_blocks blocks each; 0: 2,048 blocks, about 1.6 GB of device and 0.54 GB of pinned
+ * memory).  Every block of at most 0xff00 bytes is deflated by one wave (LZ77 in a 32-KiB window, dynamic Huffman codes, or stored where that is smaller) into a
+ * gzip member with the BC field, its CRC-32 taken on the device; the bytes are a function of the input alone.  LH_E_NODEVICE without a GPU: the compressor has
+ * no CPU fallback.  A kernel that gives up (a watchdog word) is LH_E_HIP. */
+typedef struct lh_bgzf lh_bgzf;
+int lh_bgzf_create(int device, int32_t max_blocks /* 0: default */, lh_bgzf** out);
+void lh_bgzf_free(lh_bgzf* z);
+/* cuts data[0..n) into blocks of 0xff00 bytes (the last one shorter) and writes their BGZF members, concatenated, to out; *out_len = bytes written (no end-of-file
+ * block is added).  LH_E_ARG, and nothing written, when out_cap is below lh_bgzf_bound(n).  More than max_blocks blocks go through in chunks whose transfers
+ * overlap the kernel of the chunk between them.  The call takes the compressor's mutex: several threads may share one compressor, or own one each. */
+int lh_bgzf_compress(lh_bgzf* z, const uint8_t* data, int64_t n, uint8_t* out, int64_t out_cap, int64_t* out_len);
+int64_t lh_bgzf_bound(int64_t n);   /* the most bytes the members of n bytes take: every block stored, 31 bytes each on top */
+int lh_bgzf_timings(const lh_bgzf* z, double* upload_s, double* kernel_s, double* download_s);   /* the last call's phases (device time, summed over its chunks) */
+/* z != NULL: the blocks w writes from now on are compressed by z (all files' blocks of a flush in one call); NULL: by zlib on the host threads again.  The
+ * level of lh_bam_set_level has no meaning on the device path.  A failing device call fails the writer as a zlib error does: there is no silent fall-back.
+ * z must outlive w or be taken off it first.  The end-of-file block and lh_bam_concat are the same on both paths. */
+int lh_bam_set_device(lh_bam_writer* w, lh_bgzf* z);
 
 #ifdef __cplusplus
 }

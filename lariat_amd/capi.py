@@ -586,6 +586,10 @@ class Library:
     def bam_writer(self, directory, contig_names, contig_lens, read_groups="", position_chunk_size=40000000, first_chunk=True, command_line="", threads=0):
         return BamWriter(self, directory, contig_names, contig_lens, read_groups, position_chunk_size, first_chunk, command_line, threads)
 
+    def bgzf(self, device=0, max_blocks=0):
+        """a device compressor of BGZF blocks (lh_bgzf_create)"""
+        return Bgzf(self, device, max_blocks)
+
     def records_text(self, result, ingest_batch, contig_names, debug_tags=False):
         """BAM record content (bamwriter.go AppendBam) for one batch: `result` = Result of aligning `ingest_batch`; debug_tags = -debugBamTags"""
         rs = result.as_struct()
@@ -871,6 +875,51 @@ class IngestBatch:
             pass
 
 
+class Bgzf:
+    """lh_bgzf: BGZF members compressed on the device; `.compress(bytes)` returns the members of the 0xff00-byte blocks, concatenated"""
+
+    def __init__(self, lib, device=0, max_blocks=0):
+        self.lib = lib
+        self.h = C.c_void_p()
+        L = lib.L
+        L.lh_bgzf_create.argtypes = [C.c_int, C.c_int32, C.POINTER(C.c_void_p)]
+        L.lh_bgzf_free.argtypes = [C.c_void_p]
+        L.lh_bgzf_free.restype = None
+        L.lh_bgzf_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.lh_bgzf_bound.argtypes = [C.c_int64]
+        L.lh_bgzf_bound.restype = C.c_int64
+        L.lh_bgzf_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.check(L.lh_bgzf_create(int(device), int(max_blocks), C.byref(self.h)))
+
+    def bound(self, n):
+        return int(self.lib.L.lh_bgzf_bound(int(n)))
+
+    def compress(self, data, out_cap=None):
+        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        cap = self.bound(src.size) if out_cap is None else int(out_cap)
+        out = np.empty(max(1, cap), dtype=np.uint8)
+        n_out = C.c_int64(0)
+        self.lib.check(self.lib.L.lh_bgzf_compress(self.h, src.ctypes.data if src.size else None, src.size, out.ctypes.data, cap, C.byref(n_out)))
+        return out[:n_out.value].tobytes()
+
+    def timings(self):
+        """the last compress call's phases: seconds of upload, kernel and download on the device"""
+        up, k, dl = C.c_double(), C.c_double(), C.c_double()
+        self.lib.check(self.lib.L.lh_bgzf_timings(self.h, C.byref(up), C.byref(k), C.byref(dl)))
+        return {"upload_s": up.value, "kernel_s": k.value, "download_s": dl.value}
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.lib.L.lh_bgzf_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class BamWriter:
     """the reference's set of BAM files (bamwriter.go CreateBAMs): bc_sorted_bam.bam + position buckets + ZZZ_unmapped"""
 
@@ -884,6 +933,12 @@ class BamWriter:
 
     def set_debug_tags(self, on=True):
         self.lib.check(self.lib.L.lh_bam_set_flags(self.h, LH_REC_DEBUG_TAGS if on else 0))
+
+    def set_device(self, z):
+        """blocks written from now on are compressed on the device by the Bgzf `z`; None: by zlib on the host again"""
+        self.lib.L.lh_bam_set_device.argtypes = [C.c_void_p, C.c_void_p]
+        self.lib.check(self.lib.L.lh_bam_set_device(self.h, z.h if z is not None else None))
+        self._z = z   # (the compressor must outlive its use by the writer)
 
     def append(self, result, ingest_batch):
         rs = result.as_struct()
@@ -943,4 +998,5 @@ EXPORTED_SYMBOLS = [
     "lh_index_free", "lh_index_build", "lh_context_create", "lh_context_free", "lh_align_barcodes", "lh_batch_upload", "lh_align_resident",
     "lh_result_download", "lh_result_free", "lh_last_timings", "lh_last_rounds", "lh_stage_dump_resident", "lh_stage_dump_free", "lh_get_seq", "lh_device_memory", "lh_diag_gosort", "lh_diag_gosort_split", "lh_diag_bitonic", "lh_diag_introsort", "lh_diag_random_read", "lh_diag_valu_rate", "lh_diag_rescue_sw", "lh_diag_go_rand", "lh_diag_rescue_dedup",
     "lh_index_opts_init", "lh_context_opts_init", "lh_index_build_device", "lh_index_export", "lh_index_save", "lh_synth_genome", "lh_synth_reads", "lh_synth_write_fastq9", "lh_diag_index_check", "lh_batch_upload_slot", "lh_batch_select", "lh_bam_concat", "lh_reference_pack", "lh_index_set_holes", "lh_diag_index_digest", "lh_index_set_alt", "lh_index_alt", "lh_bam_set_level", "lh_bam_timings", "lh_result_download_begin", "lh_result_download_end", "lh_batch_stage_slot", "lh_host_alloc", "lh_host_free",
+    "lh_bgzf_create", "lh_bgzf_free", "lh_bgzf_compress", "lh_bgzf_bound", "lh_bgzf_timings", "lh_bam_set_device",
 ]

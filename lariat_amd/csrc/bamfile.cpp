@@ -14,12 +14,15 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 #include "../../include/lariat_hip.h"
 
 extern "C" int lh_set_error_(int code, const char* msg);
+// the device compressor's call for several inputs at once (lh_bgzf.inc)
+extern "C" int lh_bgzf_compress_segs_(lh_bgzf* z, int32_t n_seg, const uint8_t* const* seg, const int64_t* seg_len, uint8_t* out, int64_t out_cap, int64_t* out_len, int64_t* seg_off);
 #include "records_internal.h"
 
 namespace {
@@ -84,6 +87,8 @@ struct lh_bam_writer {
     int level = Z_DEFAULT_COMPRESSION, threads = 1;
     double t_records = 0, t_join = 0, t_write = 0;   // the last lh_bam_append's phases, seconds
     bool failed = false;
+    lh_bgzf* dev = nullptr;   // lh_bam_set_device: the blocks are compressed there, not by zlib
+    std::unique_ptr<uint8_t[]> zbuf; int64_t zbuf_cap = 0;   // the device path's members of one flush: kept between flushes, never cleared
 };
 
 namespace {
@@ -161,8 +166,46 @@ int encode(const lh_bam_writer* w, const LhRec& R, std::string& rec) {
     return b[ch < b.size() ? ch : b.size() - 1];
 }
 
+// the device path of flush: the complete blocks of all files (all bytes when `all`) go to the compressor in one call, a segment per file; the files are then
+// written side by side from where their members lie
+bool flush_device(lh_bam_writer* w, bool all) {
+    const size_t n_out = w->outs.size();
+    std::vector<const uint8_t*> seg(n_out);
+    std::vector<int64_t> len(n_out), off(n_out + 1, 0);
+    int64_t cap = 0;
+    for (size_t o = 0; o < n_out; ++o) {
+        const std::string& s = w->outs[o].pending;
+        seg[o] = (const uint8_t*)s.data();
+        len[o] = (int64_t)(all ? s.size() : s.size() / BGZF_DATA * BGZF_DATA);
+        cap += lh_bgzf_bound(len[o]);
+    }
+    if (!cap) return true;
+    if (cap > w->zbuf_cap) { w->zbuf.reset(); w->zbuf_cap = 0; w->zbuf.reset(new uint8_t[(size_t)cap]); w->zbuf_cap = cap; }
+    const uint8_t* z = w->zbuf.get();
+    int64_t z_len = 0;
+    if (lh_bgzf_compress_segs_(w->dev, (int32_t)n_out, seg.data(), len.data(), w->zbuf.get(), w->zbuf_cap, &z_len, off.data())) return false;
+    std::atomic<size_t> next_out{0};
+    std::atomic<bool> all_ok{true};
+    auto write_out = [&]() {
+        for (size_t o = next_out++; o < n_out; o = next_out++) {
+            const size_t n = (size_t)(off[o + 1] - off[o]);
+            if (n && fwrite(z + off[o], 1, n, w->outs[o].f) != n) { all_ok = false; return; }
+        }
+    };
+    int wt = w->threads < 1 ? 1 : (w->threads > 16 ? 16 : w->threads);
+    if ((size_t)wt > n_out) wt = (int)n_out;
+    std::vector<std::thread> wth;
+    for (int t = 1; t < wt; ++t) wth.emplace_back(write_out);
+    write_out();
+    for (auto& t : wth) t.join();
+    if (!all_ok) { lh_set_error_(LH_E_IO, "write failed"); return false; }
+    for (size_t o = 0; o < n_out; ++o) if (len[o]) w->outs[o].pending.erase(0, (size_t)len[o]);
+    return true;
+}
+
 // compresses and writes every complete block of every file (all of it when `all`), blocks in parallel
 bool flush(lh_bam_writer* w, bool all) {
+    if (w->dev) return flush_device(w, all);
     struct Job { int out; size_t off, n; std::string z; bool ok = true; };
     std::vector<Job> jobs;
     for (size_t o = 0; o < w->outs.size(); ++o) {
@@ -275,6 +318,11 @@ extern "C" int lh_bam_set_level(lh_bam_writer* w, int32_t level) {
     w->level = level;
     return LH_OK;
 }
+extern "C" int lh_bam_set_device(lh_bam_writer* w, lh_bgzf* z) {
+    if (!w) return lh_set_error_(LH_E_ARG, "lh_bam_set_device: null writer");
+    w->dev = z;
+    return LH_OK;
+}
 extern "C" int lh_bam_timings(const lh_bam_writer* w, double* records_s, double* join_s, double* write_s) {
     if (!w) return lh_set_error_(LH_E_ARG, "lh_bam_timings: null writer");
     if (records_s) *records_s = w->t_records;
@@ -330,7 +378,11 @@ extern "C" int lh_bam_append(lh_bam_writer* w, const lh_result* res, const lh_in
         for (auto& t : th) t.join();
     }
     double t3 = now();
-    if (!flush(w, false)) { w->failed = true; return lh_set_error_(LH_E_IO, "lh_bam_append: compression or write failed"); }
+    if (!flush(w, false)) {
+        w->failed = true;
+        const std::string why = w->dev ? std::string("lh_bam_append: compression on the device or write failed: ") + lh_last_error() : std::string("lh_bam_append: compression or write failed");
+        return lh_set_error_(LH_E_IO, why.c_str());
+    }
     w->t_records = t1 - t0; w->t_join = t3 - t2; w->t_write = now() - t3;   // lh_bam_timings
     return LH_OK;
 }

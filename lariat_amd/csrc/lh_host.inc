@@ -958,3 +958,5 @@ void lh_stage_dump_free(lh_stage_dump* d) { if (d) delete (DumpArenaH*)d->arena_
 #include "lh_host_stage2.inc"
 
 #include "lh_lanes.inc"
+
+#include "lh_bgzf.inc"   // the device compressor of BGZF members (lh_bgzf_*), an object of its own
