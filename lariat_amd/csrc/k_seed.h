@@ -1,5 +1,5 @@
-// k_seed.h — K2: SA lookups (bwt_sa) for every sampled occurrence of every SMEM interval, one LANE per seed,
-// plus the exclusive scan that sizes the seed pool.  Replaces the `bwt_sa` / `bns_intv2rid` part of BWA's mem_chain
+// k_seed.h — K2: SA lookups (bwt_sa) for every sampled occurrence of every SMEM interval, one 16-lane group per read
+// (k_seed_grp; LH_F_SEED_LANE: one LANE per seed, k_seed_owner + k_seed), plus the exclusive scan that sizes the seed pool.  Replaces the `bwt_sa` / `bns_intv2rid` part of BWA's mem_chain
 // (reached through mem_align1_core, go/src/gobwa/gobwa.go:244,253).
 // Each lane chases ~sa_intv/2 dependent LF steps, every step one random 64-B occurrence block: pure HBM latency,
 // hidden by running one independent chain per lane.
@@ -9,6 +9,7 @@
 struct DSeed { i64 rbeg; int32_t qbeg, len; };
 
 // exclusive scan out[i] = sum_{j<i} max(in[j] + add, at_least), out[n] = total, in three launches:
+// (out2, if given: out2[i] = out[i] + i * add2, the scan of in[j] + add + add2 where at_least does not bind — the region slots from the seed counts)
 //   k_scan_partial (per 2048-element tile: tile sums) -> k_scan_tiles (one workgroup scans the tile sums) -> k_scan_final.
 #define LH_SCAN_TILE 2048
 __device__ __forceinline__ i64 scan_val(const int32_t* in, int i, int n, int add, int at_least) {
@@ -55,7 +56,7 @@ __global__ void __launch_bounds__(256) k_scan_tiles(int n_tiles, i64* __restrict
     if (t == 0) tile_sum[n_tiles] = carry_s;
 }
 __global__ void __launch_bounds__(256) k_scan_final(int n, const int32_t* __restrict__ in, int add, int at_least, const i64* __restrict__ tile_sum, int n_tiles,
-                                                    i64* __restrict__ out) {
+                                                    i64* __restrict__ out, i64* __restrict__ out2, int add2) {
     __shared__ i64 part[256];
     int t = threadIdx.x, base = blockIdx.x * LH_SCAN_TILE + t * 8;
     i64 loc[8], s = 0;
@@ -71,9 +72,13 @@ __global__ void __launch_bounds__(256) k_scan_final(int n, const int32_t* __rest
     i64 excl = part[t] - s + tile_sum[blockIdx.x];
     for (int u = 0; u < 8; ++u) if (base + u < n) out[base + u] = excl + loc[u];
     if (blockIdx.x == 0 && t == 0) out[n] = tile_sum[n_tiles];
+    if (out2) {
+        for (int u = 0; u < 8; ++u) if (base + u < n) out2[base + u] = excl + loc[u] + (i64)(base + u) * add2;
+        if (blockIdx.x == 0 && t == 0) out2[n] = tile_sum[n_tiles] + (i64)n * add2;
+    }
 }
 
-// owner[g] = the read seed slot g belongs to (one lane per read writes its few slots): spares K2 a 21-step binary search per seed
+// (LH_F_SEED_LANE) owner[g] = the read seed slot g belongs to (one lane per read writes its few slots): spares k_seed a 21-step binary search per seed
 __global__ void __launch_bounds__(256) k_seed_owner(int n_reads, const i64* __restrict__ seed_off, i64 pool_cap, int32_t* __restrict__ owner) {
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += gridDim.x * blockDim.x) {
         i64 e = seed_off[r + 1] < pool_cap ? seed_off[r + 1] : pool_cap;
@@ -81,7 +86,7 @@ __global__ void __launch_bounds__(256) k_seed_owner(int n_reads, const i64* __re
     }
 }
 
-// K2.  one lane per seed; grid-stride over the pool.
+// K2 under LH_F_SEED_LANE.  one lane per seed; grid-stride over the pool.
 __global__ void __launch_bounds__(256) k_seed(DIndex ix, DOpts o, int n_reads, const i64* __restrict__ seed_off, i64 pool_cap,
                                               const DIntv* __restrict__ intv, const int32_t* __restrict__ n_intv, DSeed* __restrict__ seeds,
                                               int32_t* __restrict__ s_rid, DCounters* __restrict__ ctr, const int32_t* __restrict__ owner,
@@ -125,5 +130,92 @@ __global__ void __launch_bounds__(256) k_seed(DIndex ix, DOpts o, int n_reads, c
             int tl = wave_sum_i32(nlf), ts = wave_sum_i32(nsa);
             if (LANE() == 0 && ts) { atomicAdd(&LH_CTR(ctr)->n_lf, (u64)tl); atomicAdd(&LH_CTR(ctr)->n_sa, (u64)ts); }
         }
+    }
+}
+
+// the seeds an interval of s occurrences yields (mem_chain: every step-th occurrence, at most max_occ) and the step between them
+__device__ __forceinline__ u64 dev_seed_step(const DOpts& o, u64 s, u64* step) {
+    *step = 1;
+    if (s <= (u64)o.max_occ) return s;   // (the usual interval has at most max_occ occurrences: every one is a seed; the 64-bit divisions are for the others)
+    const u64 st = s / (u64)o.max_occ, c = (s + st - 1) / st;
+    *step = st;
+    return c < (u64)o.max_occ ? c : (u64)o.max_occ;
+}
+
+// K2.  One 16-lane group per read, four reads per wave, the waves grid-stride over the batch.  The group takes the read's sorted intervals 16 at a time, lane `sub`
+// entry sub + 16t of chunk t (k_smem_fin's layout): each lane counts its entry's seeds, a prefix over the row places them, and the chunk — position, query span,
+// step, prefix: 28 B an entry, 1,792 B of LDS a wave — is staged in LDS.  The 16 lanes then stride over the chunk's seed slots: a slot finds its interval by four
+// look-ups in the staged prefix and reads its entry there, so an interval is read from memory once, a repeat interval's up-to-max_occ occurrences and a unique read's
+// ten intervals of one both keep their lanes busy, and sixteen consecutive slots are one write.  Seeds, their order (intervals in `info` order, occurrences
+// u = 0 .. c-1 within each), the clamp at pool_cap and the counters are k_seed's.  Every cross-lane step is reached by the whole wave: trip counts are the wave's maxima.
+struct K2Intv { u64 x0, x2, info; };   // what K2 reads of an interval
+__device__ __forceinline__ K2Intv k2_load(const DIntv* __restrict__ iv, int e, int n) {
+    K2Intv m;
+    m.x0 = m.x2 = m.info = 0;
+    if (e < n) { m.x0 = iv[e].x0; m.x2 = iv[e].x2; m.info = iv[e].info; }
+    return m;
+}
+#define LH_K2_GRID 16384   // waves of k_seed_grp: about twice what the device holds at eight waves per SIMD, so that the last ones to finish are short of work for less time
+__global__ void __launch_bounds__(64) k_seed_grp(DIndex ix, DOpts o, int n_reads, const i64* __restrict__ seed_off, i64 pool_cap, const DIntv* __restrict__ intv,
+                                                 const int32_t* __restrict__ n_intv, DSeed* __restrict__ seeds, int32_t* __restrict__ s_rid, DCounters* __restrict__ ctr,
+                                                 const int32_t* __restrict__ big_slot, const DIntv* __restrict__ big_slab) {
+    __shared__ u64 sh_x0[64], sh_info[64], sh_step[64];
+    __shared__ int sh_incl[64];
+    const int lane = LANE(), sub = lane & 15, row = lane & ~15;
+    const int n_items = (n_reads + 3) >> 2;
+    int nlf = 0, nsa = 0;
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int r = item * 4 + (lane >> 4);
+        const bool live = r < n_reads;
+        int n = 0, S = 0;   // S: the read's seed slots below pool_cap
+        i64 base = 0;
+        const DIntv* iv = intv;
+        if (live) {
+            n = n_intv[r];
+            base = seed_off[r];
+            const i64 end = seed_off[r + 1] < pool_cap ? seed_off[r + 1] : pool_cap;
+            S = end > base ? (int)(end - base) : 0;
+            const int bs = big_slot ? big_slot[r] : -1;   // (a read with more than LH_MAX_INTV intervals: the sorted half of its big-slab slot, k_smem4.h)
+            iv = bs < 0 ? intv + (size_t)r * LH_MAX_INTV : big_slab + ((size_t)bs * 2 + 1) * LH_BIG_INTV;
+        }
+        const int n_chunks = wave_max_i32((n + 15) >> 4);
+        int run = 0;   // seeds of the chunks before this one
+        for (int ch = 0; ch < n_chunks; ++ch) {
+            const bool have = ch * 16 + sub < n;
+            const K2Intv m = k2_load(iv, ch * 16 + sub, n);
+            u64 m_step = 1;
+            const int cnt = have ? (int)dev_seed_step(o, m.x2, &m_step) : 0;
+            EMU_SYNC();   // (the slots of the chunk before have read theirs)
+            sh_x0[lane] = m.x0; sh_info[lane] = m.info; sh_step[lane] = m_step; sh_incl[lane] = row_scan_add_i32(cnt);
+            EMU_SYNC();
+            const int tot = sh_incl[row | 15];
+            const int n_iter = wave_max_i32((tot + 15) >> 4);
+            for (int it = 0; it < n_iter; ++it) {
+                const int k = it * 16 + sub;   // the slot inside the chunk
+                int j = 0;                     // its interval: the entries of the row whose prefix is <= k
+#pragma unroll
+                for (int w = 8; w >= 1; w >>= 1) j += sh_incl[row | (j + w - 1)] <= k ? w : 0;
+                const int src = row | j;
+                if (k < tot && run + k < S) {
+                    const int u = k - (j ? sh_incl[src - 1] : 0);   // the occurrence inside the interval
+                    const u64 x0 = sh_x0[src], st = sh_step[src], info = sh_info[src];
+                    i64 rbeg;
+                    if (x0 >> 62 & 1) rbeg = (i64)(x0 & ~(1ull << 62));   // K1 stored the interval's one occurrence by its text position (LH_POSF, k_smem4.h)
+                    else { int lf = 0; rbeg = (i64)dev_sa(ix, x0 + (u64)u * st, &lf); nlf += lf; }
+                    ++nsa;   // (n_sa counts the reference's bwt_sa calls: one per seed)
+                    const int qbeg = (int)(info >> 32), slen = (int)(uint32_t)info - qbeg;
+                    DSeed sd;
+                    sd.rbeg = rbeg; sd.qbeg = qbeg; sd.len = slen;
+                    const i64 g = base + run + k;
+                    seeds[g] = sd;
+                    s_rid[g] = dev_intv2rid(ix, rbeg, rbeg + slen);
+                }
+            }
+            run += tot;
+        }
+    }
+    if (ctr) {
+        const int tl = wave_sum_i32(nlf), ts = wave_sum_i32(nsa);
+        if (lane == 0 && ts) { atomicAdd(&LH_CTR(ctr)->n_lf, (u64)tl); atomicAdd(&LH_CTR(ctr)->n_sa, (u64)ts); }
     }
 }

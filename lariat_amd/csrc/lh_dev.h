@@ -28,7 +28,7 @@ struct uint2 { uint32_t x, y; };
 #define LH_WAVE 64
 #define LH_MAXLEN 250            // LH_MAX_READ_LEN
 #ifndef LH_MAX_INTV
-#define LH_MAX_INTV 64           // SMEM intervals kept per read in its regular slots; a read with more is seeded again into a big slab (k_smem4.h, BIG) — tests build with 4
+#define LH_MAX_INTV 64           // SMEM intervals kept per read in its regular slots; a read with more is seeded again into a big slab (k_smem4.h, BIG) — the emulator's `small` build and the seed-group tests' variant have 4
 #endif
 #define LH_BIG_INTV 1024         // ... which holds this many per read (mem_collect_intv yields at most ~250 for 250 bases outside pathological re-seeding); beyond: LH_ST_INTV_OVERFLOW
 #define LH_MAX_CIGAR 64          // cigar ops per candidate
@@ -189,6 +189,12 @@ __device__ __forceinline__ int wave_scan_add_i32(int v) {
     for (int d = 1; d < 64; d <<= 1) { int o = __shfl_up(v, d); if (lane >= d) v += o; }
     return v;
 }
+// inclusive prefix sum inside each 16-lane row
+__device__ __forceinline__ int row_scan_add_i32(int v) {
+    int sub = LANE() & 15;
+    for (int d = 1; d < 16; d <<= 1) { int o = __shfl_up(v, d); if (sub >= d) v += o; }
+    return v;
+}
 __device__ __forceinline__ int wave_shr1_i32(int v, int fill) { int o = __shfl_up(v, 1); return LANE() == 0 ? fill : o; }   // lane i <- lane i-1
 __device__ __forceinline__ int wave_readlane(int v, int l) { return __shfl(v, l); }                                          // l must be wave-uniform
 #else
@@ -217,6 +223,13 @@ __device__ __forceinline__ int wave_scan_add_i32(int v) {   // inclusive prefix 
     v += LH_DPP(0, v, 0x118, 0xF);
     v += LH_DPP(0, v, 0x142, 0xA);
     v += LH_DPP(0, v, 0x143, 0xC);
+    return v;
+}
+__device__ __forceinline__ int row_scan_add_i32(int v) {   // inclusive prefix sum inside each 16-lane row (the row steps of the above)
+    v += LH_DPP(0, v, 0x111, 0xF);
+    v += LH_DPP(0, v, 0x112, 0xF);
+    v += LH_DPP(0, v, 0x114, 0xF);
+    v += LH_DPP(0, v, 0x118, 0xF);
     return v;
 }
 __device__ __forceinline__ int wave_sum_i32(int v) {

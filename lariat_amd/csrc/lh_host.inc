@@ -448,11 +448,11 @@ static int pipe_select(lh_context* c, int32_t slot) {
         ++t;                                                                                     \
     } while (0)
 
-static int run_scan(lh_context* c, int n, const int32_t* in, int add, int at_least, i64* out) {
+static int run_scan(lh_context* c, int n, const int32_t* in, int add, int at_least, i64* out, i64* out2 = nullptr, int add2 = 0) {
     int nt = (n + LH_SCAN_TILE - 1) / LH_SCAN_TILE;
     LH_LAUNCH(k_scan_partial, nt, 256, c->stream, n, in, add, at_least, c->d_tile_sum);
     LH_LAUNCH(k_scan_tiles, 1, 256, c->stream, nt, c->d_tile_sum);
-    LH_LAUNCH(k_scan_final, nt, 256, c->stream, n, in, add, at_least, c->d_tile_sum, nt, out);
+    LH_LAUNCH(k_scan_final, nt, 256, c->stream, n, in, add, at_least, c->d_tile_sum, nt, out, out2, add2);
     return LH_OK;
 }
 
@@ -562,7 +562,8 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         T_END();
     }
     T_BEGIN("k_scan_seeds");
-    { int rc = run_scan(c, N, c->d_seed_cnt, 0, 0, c->d_seed_off); if (rc) return rc; }
+    // ... and with them the region slots of a read, one per seed + the rescue slots: reg_off[i] = seed_off[i] + i * LH_RESCUE_SLOTS
+    { int rc = run_scan(c, N, c->d_seed_cnt, 0, 0, c->d_seed_off, c->d_reg_off, LH_RESCUE_SLOTS); if (rc) return rc; }
     T_END();
     {   // the seed pools (and the region pools derived from them) follow the batch: grow them before anything writes there
         { int rc = peek_seed_total(c, N); if (rc) return rc; }
@@ -581,7 +582,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
             grown.release();
             c->big_base = (int)old_cap; c->big_cap = (int)new_cap;
             { int rc = k1_big_round(c, o, ix4, N, c->big_base); if (rc) return rc; }
-            { int rc = run_scan(c, N, c->d_seed_cnt, 0, 0, c->d_seed_off); if (rc) return rc; }
+            { int rc = run_scan(c, N, c->d_seed_cnt, 0, 0, c->d_seed_off, c->d_reg_off, LH_RESCUE_SLOTS); if (rc) return rc; }
             { int rc = peek_seed_total(c, N); if (rc) return rc; }
         }
         c->big_base = 0;
@@ -606,12 +607,15 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         }
     }
     T_BEGIN("k_seed");
-    int g2 = (int)((i64)N * 8 / 256 + 1); if (g2 > 2048) g2 = 2048;
-    LH_LAUNCH(k_seed_owner, (N + 255) / 256 < 8192 ? (N + 255) / 256 : 8192, 256, c->stream, N, (const i64*)c->d_seed_off, c->pool_cap, c->d_s_next);   // d_s_next is K3's: free until then
-    LH_LAUNCH(k_seed, g2, 256, c->stream, ix, o, N, c->d_seed_off, c->pool_cap, c->d_intv, c->d_n_intv, c->d_seeds, c->d_s_rid, c->d_ctr, (const int32_t*)c->d_s_next, (const int32_t*)c->d_big_slot, (const DIntv*)c->d_big_slab);
-    T_END();
-    T_BEGIN("k_scan_regs");
-    { int rc = run_scan(c, N, c->d_seed_cnt, LH_RESCUE_SLOTS, 0, c->d_reg_off); if (rc) return rc; }   // the region slots of a read: one per seed + the rescue slots
+    if (c->flags & LH_F_SEED_LANE) {   // one lane per seed (the A/B leg)
+        int g2 = (int)((i64)N * 8 / 256 + 1); if (g2 > 2048) g2 = 2048;
+        LH_LAUNCH(k_seed_owner, (N + 255) / 256 < 8192 ? (N + 255) / 256 : 8192, 256, c->stream, N, (const i64*)c->d_seed_off, c->pool_cap, c->d_s_next);   // d_s_next is K3's: free until then
+        LH_LAUNCH(k_seed, g2, 256, c->stream, ix, o, N, c->d_seed_off, c->pool_cap, c->d_intv, c->d_n_intv, c->d_seeds, c->d_s_rid, c->d_ctr, (const int32_t*)c->d_s_next, (const int32_t*)c->d_big_slot, (const DIntv*)c->d_big_slab);
+    } else {   // a 16-lane group per read, four reads to a wave
+        const int items = (N + 3) / 4;
+        LH_LAUNCH(k_seed_grp, items < LH_K2_GRID ? items : LH_K2_GRID, 64, c->stream, ix, o, N, (const i64*)c->d_seed_off, c->pool_cap, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_seeds, c->d_s_rid, c->d_ctr,
+                  (const int32_t*)c->d_big_slot, (const DIntv*)c->d_big_slab);
+    }
     T_END();
     T_BEGIN("k_chain");
     HIPCHK(hipMemsetAsync(c->d_ext_jobs, 0, sizeof(DExtJobs), c->stream));
@@ -829,7 +833,7 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
     if (!c->resident) return set_err(LH_E_ARG, "no batch resident: call lh_batch_upload first");
     if (opts->abi_version != LH_ABI_VERSION) return set_err(LH_E_ARG, "lh_opts.abi_version does not match LH_ABI_VERSION (use lh_opts_init)");
-    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
+    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
     HIPCHK(hipSetDevice(c->idx->device));
     {
         std::vector<void*> fl;
