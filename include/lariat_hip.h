@@ -80,7 +80,7 @@ typedef struct lh_opts {
 #define LH_F_EXT_SERIAL 32u      /* K4's rounds and wave-kernel launches one after the other on one stream (per-round timings) */
 #define LH_F_P2_TASKS 128u       /* K1 pass 2: a read's re-seeding calls shared by up to four lanes whatever the previous batch looked like (default: only after a repeat-rich batch) */
 #define LH_F_RESCUE_FULL 256u     /* K6: every mate-rescue Smith-Waterman runs all rows of its window (default: the rows k_resc_cert proves sufficient, k_rescue3.h) */
-#define LH_F_SEED_LANE 512u       /* (ABI 7) K2: one lane per seed after a pass that names every seed slot's read (k_seed_owner + k_seed; default: a 16-lane group per read, k_seed_grp) */
+#define LH_F_SEED_LANE 512u       /* (ABI 7) K2: one lane per seed after a pass that names every seed slot's read (k_seed_owner + k_seed) and k_smem_fin sorting every read's intervals in memory before it; default: a 16-lane group per read that ranks its intervals itself, k_seed_grp */
 #define LH_F_CHAIN_WAVE 64u      /* K3: the reads a lane does not chain all go to the wave-per-seed kernel (k_chain), none to the cluster kernel (k_chain_cl) */
 
 /* how an index is made resident (lh_index_load / lh_index_from_arrays / lh_index_build_device); NULL = defaults */

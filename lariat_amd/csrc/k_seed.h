@@ -155,6 +155,20 @@ __device__ __forceinline__ K2Intv k2_load(const DIntv* __restrict__ iv, int e, i
     if (e < n) { m.x0 = iv[e].x0; m.x2 = iv[e].x2; m.info = iv[e].info; }
     return m;
 }
+// the number of keys of the lane's 16-lane row that are below its own (the keys of a row differ: the rank of each is its place in their order)
+__device__ __forceinline__ int row_rank_u32(uint32_t key) {
+    int rank = 0;
+#ifdef LH_EMU
+    const int lane = LANE();
+    for (int d = 1; d < 16; ++d) rank += __shfl(key, (lane & ~15) | ((lane + d) & 15)) < key;
+#else
+#define LH_ROW_ROR(d) rank += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)key, 0x120 + (d), 0xF, 0xF, true) < key;   // row_ror:d
+    LH_ROW_ROR(1) LH_ROW_ROR(2) LH_ROW_ROR(3) LH_ROW_ROR(4) LH_ROW_ROR(5) LH_ROW_ROR(6) LH_ROW_ROR(7) LH_ROW_ROR(8)
+    LH_ROW_ROR(9) LH_ROW_ROR(10) LH_ROW_ROR(11) LH_ROW_ROR(12) LH_ROW_ROR(13) LH_ROW_ROR(14) LH_ROW_ROR(15)
+#undef LH_ROW_ROR
+#endif
+    return rank;
+}
 #define LH_K2_GRID 16384   // waves of k_seed_grp: about twice what the device holds at eight waves per SIMD, so that the last ones to finish are short of work for less time
 __global__ void __launch_bounds__(64) k_seed_grp(DIndex ix, DOpts o, int n_reads, const i64* __restrict__ seed_off, i64 pool_cap, const DIntv* __restrict__ intv,
                                                  const int32_t* __restrict__ n_intv, DSeed* __restrict__ seeds, int32_t* __restrict__ s_rid, DCounters* __restrict__ ctr,
@@ -185,8 +199,19 @@ __global__ void __launch_bounds__(64) k_seed_grp(DIndex ix, DOpts o, int n_reads
             const K2Intv m = k2_load(iv, ch * 16 + sub, n);
             u64 m_step = 1;
             const int cnt = have ? (int)dev_seed_step(o, m.x2, &m_step) : 0;
+            // a read of at most 16 intervals arrives as K1 emitted it (pass 3 has counted it: no k_smem_fin): its one chunk is ranked here by (info, slot) — query
+            // span and slot are one 32-bit key, LH_MAXLEN < 256 — and staged at its rank, lanes without an entry last.  Rows of more intervals were sorted in
+            // memory and keep their places, as sorted input would anyway
+            int pos = lane;
+            if (ch == 0) {
+                const uint32_t key = n > 16 ? (uint32_t)sub : !have ? 0xfffffff0u | (uint32_t)sub : (uint32_t)(m.info >> 32) << 12 | ((uint32_t)m.info & 0xffu) << 4 | (uint32_t)sub;
+                pos = row | row_rank_u32(key);
+            }
             EMU_SYNC();   // (the slots of the chunk before have read theirs)
-            sh_x0[lane] = m.x0; sh_info[lane] = m.info; sh_step[lane] = m_step; sh_incl[lane] = row_scan_add_i32(cnt);
+            sh_x0[pos] = m.x0; sh_info[pos] = m.info; sh_step[pos] = m_step; sh_incl[pos] = cnt;
+            EMU_SYNC();
+            const int incl = row_scan_add_i32(sh_incl[lane]);   // (a lane's own word: nobody else reads it before the next rendezvous)
+            sh_incl[lane] = incl;
             EMU_SYNC();
             const int tot = sh_incl[row | 15];
             const int n_iter = wave_max_i32((tot + 15) >> 4);

@@ -1237,23 +1237,34 @@ __device__ __forceinline__ int dev_seed_count(const DOpts& o, u64 s) {
     u64 c = (s + step - 1) / step;
     return (int)(c < (u64)o.max_occ ? c : (u64)o.max_occ);
 }
+// what an interval of s occurrences adds to pass 3's one word of counting: its occurrences, and LH_CNT_REP if they are more than max_occ (a saturating add would do
+// no better: a read whose word reaches LH_CNT_REP is counted again by k_smem_fin)
+#define LH_CNT_REP 0x1000000u
+#define LH_CNT_OVF 0x80000000u
+__device__ __forceinline__ uint32_t dev_cnt_acc(const DOpts& o, u64 s) { return s > (u64)o.max_occ || s >= LH_CNT_REP ? LH_CNT_REP : (uint32_t)s; }
 // PASS 3 IN LOCKSTEP, one thread per read (new in r03).  bwt_seed_strategy1 is a forward-only loop — no interval lists, no sweeps — so
 // it needs no state machine: every thread walks its own read, the threads of a wave in the same short loop.  Same shortcuts as the
 // pass-3 state machine (k_smem_pass<3>): a walk that starts inside one of the read's unique SMEMs is one PLCP byte (P3TEXT), any other
 // takes its first bases from the k-mer tree table and goes on through the occurrence table.  Measured: 0.1 G wave-instructions at
 // ~40 active lanes for what cost the state machine 1.2 G at 24.
 __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_reads, const uint32_t* __restrict__ q4, const i64* __restrict__ seq_off, DIntv* __restrict__ intv_out,
-                                                       int32_t* __restrict__ n_intv, int32_t* __restrict__ status, DCounters* __restrict__ ctr) {
+                                                       int32_t* __restrict__ n_intv, int32_t* __restrict__ status, DCounters* __restrict__ ctr,
+                                                       int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep, int32_t* __restrict__ fin_list, int32_t* __restrict__ fin_count) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
     const PEnt* const kt = (const PEnt*)ix.ktree;
     const int ktl = kt ? ix.ktree_levels : 0;
     const int Lw = o.min_seed_len + 1;
     const bool text_ok = ix.isa != nullptr && ix.plcp != nullptr && o.max_mem_intv > 1;
     unsigned n_ext = 0, n_exec = 0, n_kt = 0;
+    // one word of state beside the walk (a second one costs this kernel a wave per SIMD).  Bit 31: an interval found no slot.  Below it, if seed_cnt is given: the read's
+    // seeds while none of its intervals has more than max_occ occurrences (every occurrence is a seed then: dev_seed_count without its 64-bit divisions); an interval
+    // that has adds LH_CNT_REP, and the read is listed for k_smem_fin, which counts it properly
+    uint32_t cnt = 0;
+    int fin = 0;
     if (r < n_reads) {
         const i64 off = seq_off[r];
         int len = (int)(seq_off[r + 1] - off);
-        int rst = status[r], on = n_intv[r], ovf = 0;
+        int on = n_intv[r];
         if (len > LH_MAXLEN) len = 0;
         DIntv* out = intv_out + (size_t)r * LH_MAX_INTV;
 #define QN(i_) ((int)(dev_nib8(q4, off + (i_)) & 0xf))
@@ -1264,11 +1275,14 @@ __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_
             if (text_ok)
                 for (int k = 0; k < on; ++k) {
                     const DIntv p = out[k];
+                    if (seed_cnt) cnt += dev_cnt_acc(o, p.x2);
                     const int ps = (int)(p.info >> 32), pe = (int)(uint32_t)p.info;
                     if (p.x2 != 1 || pe - ps < Lw) continue;
                     if (pe - ps > ue0 - us0) { us1 = us0; ue1 = ue0; up1 = up0; us0 = ps; ue0 = pe; up0 = p.x0; }
                     else if (pe - ps > ue1 - us1) { us1 = ps; ue1 = pe; up1 = p.x0; }
                 }
+            else if (seed_cnt)
+                for (int k = 0; k < on; ++k) cnt += dev_cnt_acc(o, out[k].x2);
             if (ue0 > us0) up0 = (up0 & LH_POSF) ? up0 & ~LH_POSF : ix.sa[up0];
             if (ue1 > us1) up1 = (up1 & LH_POSF) ? up1 & ~LH_POSF : ix.sa[up1];
             int x = 0, notext = 0;
@@ -1278,8 +1292,11 @@ __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_
                 if (text_ok && !notext && (in0 || in1)) {   // by text: unique iff the suffix there shares fewer than Lw bases with every other one
                     const i64 tp = in0 ? (i64)up0 + (x - us0) : (i64)up1 + (x - us1);
                     if ((int)ix.plcp[tp] < Lw) {
-                        if (on >= LH_MAX_INTV) ovf = 1;
-                        else { DIntv m; m.x0 = LH_POSF | (u64)tp; m.x1 = 0; m.x2 = 1; m.info = (u64)x << 32 | (u64)(x + Lw); out[on++] = m; }
+                        if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
+                        else {
+                            DIntv m; m.x0 = LH_POSF | (u64)tp; m.x1 = 0; m.x2 = 1; m.info = (u64)x << 32 | (u64)(x + Lw); out[on++] = m;
+                            if (seed_cnt) cnt += dev_cnt_acc(o, 1);
+                        }
                         n_ext += (unsigned)(Lw - 1);
                         x += Lw;
                         continue;
@@ -1322,8 +1339,11 @@ __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_
                     ++n_ext;
                     if (ok.x2 < (u64)o.max_mem_intv && i - x >= o.min_seed_len) {
                         if (ok.x2 > 0) {
-                            if (on >= LH_MAX_INTV) ovf = 1;
-                            else { ok.info = (u64)x << 32 | (u64)(i + 1); out[on++] = ok; }
+                            if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
+                            else {
+                                ok.info = (u64)x << 32 | (u64)(i + 1); out[on++] = ok;
+                                if (seed_cnt) cnt += dev_cnt_acc(o, ok.x2);
+                            }
                         }
                         nx = i + 1;
                         break;
@@ -1332,11 +1352,25 @@ __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_
                 }
                 x = nx;
             }
-        }
+        } else if (seed_cnt)   // a read pass 3 does not walk (no bases, too short, too long) is counted all the same
+            for (int k = 0; k < on; ++k) cnt += dev_cnt_acc(o, out[k].x2);
 #undef QN
-        if (ovf) rst |= LH_ST_INTV_OVERFLOW;
+        if (cnt & LH_CNT_OVF) status[r] |= LH_ST_INTV_OVERFLOW;
         n_intv[r] = on;
-        status[r] = rst;
+        if (seed_cnt) {
+            // the counts k_smem_fin would find.  K2 ranks a read of at most 16 intervals inside its group (k_seed.h); the others, and those whose count and l_rep need
+            // the sampling of an interval above max_occ, are listed for k_smem_fin, which overwrites both words.  (A read that overflowed may be listed too:
+            // k_smem_fin skips it once it has a big-slab slot, and k_smem_fin_big writes its words)
+            seed_cnt[r] = (int)(cnt & (LH_CNT_REP - 1)); l_rep[r] = 0;
+            fin = on > 16 || (cnt & ~LH_CNT_OVF) >= LH_CNT_REP;
+        }
+    }
+    if (seed_cnt) {   // one append per wave, the lanes at their prefix
+        const u64 m = __ballot(fin);
+        int base = 0;
+        if (lane == 0 && m) base = atomicAdd(fin_count, __popcll(m));
+        base = wave_readlane(base, 0);
+        if (fin) fin_list[base + lanes_below(m, lane)] = r;
     }
     if (ctr) {
         unsigned t1 = (unsigned)wave_sum_i32((int)n_ext), t2 = (unsigned)wave_sum_i32((int)n_exec), t3 = (unsigned)wave_sum_i32((int)n_kt);
@@ -1345,44 +1379,52 @@ __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_
 }
 
 // sort each read's intervals by info (rank sort; equal keys are identical intervals), seed counts, l_rep.  16 lanes per read
-// (reads in the big slab: k_smem_fin_big).
+// (reads in the big slab: k_smem_fin_big).  list: only those reads (k_smem_p3_lock's: more than 16 intervals, or one above max_occ; the others K2 ranks itself and
+// pass 3 has counted), *list_count of them; else every read.  The blocks stride over the groups of 16 items, each trip reached by a block's every thread.
+#define LH_FIN_GRID 4096   // blocks of a launch over a list (its length is known on the device only)
 __global__ void __launch_bounds__(256) k_smem_fin(DOpts o, int n_reads, DIntv* __restrict__ intv, const int32_t* __restrict__ n_intv, int32_t* __restrict__ seed_cnt,
-                                                   int32_t* __restrict__ l_rep_out, const int32_t* __restrict__ big_slot) {
-    int gid = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    int r = gid < n_reads ? gid : n_reads - 1;
-    int live = gid < n_reads && !(big_slot && big_slot[r] >= 0);
-    DIntv* a = intv + (size_t)r * LH_MAX_INTV;
-    int n = live ? n_intv[r] : 0;
-    DIntv mine[4];
-    int rank[4];
-    for (int t = 0; t < 4; ++t) {
-        int e = sub + 16 * t;
-        mine[t].x0 = mine[t].x1 = mine[t].x2 = 0; mine[t].info = ~0ull;
-        if (e < n) mine[t] = a[e];
-        rank[t] = 0;
-    }
-    const int nt = (n + 15) >> 4;   // slots in use (one for the usual dozen intervals: the others' compares are skipped by the whole wave)
-    for (int u = 0; u < n; ++u) {
-        u64 oi = a[u].info;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (t < nt) { int e = sub + 16 * t; rank[t] += (oi < mine[t].info) || (oi == mine[t].info && u < e); }
-    }
-    __syncthreads();   // every lane holds its entries before any is overwritten
-    int cnt = 0, rep = 0;   // rep: intervals with more than max_occ occurrences (none, usually: l_rep is 0 without another walk over the intervals)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        int e = sub + 16 * t;
-        if (t < nt && e < n && live) {
-            a[rank[t]] = mine[t];
-            cnt += dev_seed_count(o, mine[t].x2);
-            rep += mine[t].x2 > (u64)o.max_occ;
+                                                   int32_t* __restrict__ l_rep_out, const int32_t* __restrict__ big_slot, const int32_t* __restrict__ list,
+                                                   const int32_t* __restrict__ list_count) {
+    const int n_items = list ? *list_count : n_reads, sub = threadIdx.x & 15;
+    for (int g0 = blockIdx.x * (blockDim.x >> 4); g0 < n_items; g0 += gridDim.x * (blockDim.x >> 4)) {
+        const int gid = g0 + (threadIdx.x >> 4);
+        const int item = gid < n_items ? gid : n_items - 1;
+        const int r = list ? list[item] : item;
+        // (a read with a big-slab slot: its n_intv counts the slab's intervals, and k_smem_fin_big has written its counts)
+        const int live = gid < n_items && !(big_slot && big_slot[r] >= 0);
+        DIntv* a = intv + (size_t)r * LH_MAX_INTV;
+        const int n = live ? n_intv[r] : 0;
+        DIntv mine[4];
+        int rank[4];
+        for (int t = 0; t < 4; ++t) {
+            int e = sub + 16 * t;
+            mine[t].x0 = mine[t].x1 = mine[t].x2 = 0; mine[t].info = ~0ull;
+            if (e < n) mine[t] = a[e];
+            rank[t] = 0;
         }
+        const int nt = (n + 15) >> 4;   // slots in use (one for the usual dozen intervals: the others' compares are skipped by the whole wave)
+        for (int u = 0; u < n; ++u) {
+            u64 oi = a[u].info;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (t < nt) { int e = sub + 16 * t; rank[t] += (oi < mine[t].info) || (oi == mine[t].info && u < e); }
+        }
+        __syncthreads();   // every lane holds its entries before any is overwritten
+        int cnt = 0, rep = 0;   // rep: intervals with more than max_occ occurrences (none, usually: l_rep is 0 without another walk over the intervals)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            int e = sub + 16 * t;
+            if (t < nt && e < n && live) {
+                a[rank[t]] = mine[t];
+                cnt += dev_seed_count(o, mine[t].x2);
+                rep += mine[t].x2 > (u64)o.max_occ;
+            }
+        }
+        cnt += (int)dpp_xor1((uint32_t)cnt); cnt += (int)dpp_xor2((uint32_t)cnt); cnt += (int)dpp_half_mirror((uint32_t)cnt); cnt += (int)dpp_ror8((uint32_t)cnt);
+        rep += (int)dpp_xor1((uint32_t)rep); rep += (int)dpp_xor2((uint32_t)rep); rep += (int)dpp_half_mirror((uint32_t)rep); rep += (int)dpp_ror8((uint32_t)rep);
+        __syncthreads();
+        if (sub == 0 && live) { seed_cnt[r] = cnt; l_rep_out[r] = rep ? dev_l_rep(o, a, n) : 0; }
     }
-    cnt += (int)dpp_xor1((uint32_t)cnt); cnt += (int)dpp_xor2((uint32_t)cnt); cnt += (int)dpp_half_mirror((uint32_t)cnt); cnt += (int)dpp_ror8((uint32_t)cnt);
-    rep += (int)dpp_xor1((uint32_t)rep); rep += (int)dpp_xor2((uint32_t)rep); rep += (int)dpp_half_mirror((uint32_t)rep); rep += (int)dpp_ror8((uint32_t)rep);
-    __syncthreads();
-    if (sub == 0 && live) { seed_cnt[r] = cnt; l_rep_out[r] = rep ? dev_l_rep(o, a, n) : 0; }
 }
 // the same for a read in the big slab, one wave per read: ranks against the unsorted half, written to the sorted half
 __global__ void __launch_bounds__(64) k_smem_fin_big(DOpts o, K1Big big, const int32_t* __restrict__ n_intv, int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep_out) {

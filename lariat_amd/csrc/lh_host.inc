@@ -102,6 +102,7 @@ struct lh_context {
     DIntv* d_intv = nullptr; DIntv* d_big_slab = nullptr; int32_t *d_big_slot = nullptr, *d_big_list = nullptr; K1BigCounts* d_big_count = nullptr; int big_cap = 0, big_base = 0;   // reads with more than LH_MAX_INTV intervals (k_smem4.h BIG)
     K1Resume* d_k1_resume = nullptr; int32_t *d_k1_todo = nullptr, *d_p2_tasks = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read->n_todo)
     int32_t *d_n_intv = nullptr, *d_seed_cnt = nullptr, *d_l_rep = nullptr, *d_status = nullptr;
+    int32_t* d_fin_list = nullptr;   // the reads pass 3 leaves to k_smem_fin (the count: d_next_read->n_fin); the others' intervals K2 ranks itself
     // K2/K3
     i64* d_seed_off = nullptr; DSeed* d_seeds = nullptr; int32_t *d_s_rid = nullptr, *d_s_next = nullptr, *d_ord = nullptr, *d_srt = nullptr;
     DChainTmp* d_ct = nullptr; DChain* d_chains = nullptr; DSeed* d_cseeds = nullptr; int32_t* d_n_chains = nullptr;
@@ -312,7 +313,7 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
     c->big_cap = c->co.big_slots > 0 ? c->co.big_slots : LH_MAX_INTV < 16 ? (int)N : (int)(N / 256 > 64 ? N / 256 : 64);   // (a test build with tiny regular slots sends most reads there)
     DALLOC(g, c->d_k1_resume, N); DALLOC(g, c->d_k1_todo, N); DALLOC(g, c->d_p2_tasks, (size_t)LH_P2_SPLIT * N);
     DALLOC(c->big_mem, c->d_big_slab, (size_t)c->big_cap * 2 * LH_BIG_INTV); DALLOC(g, c->d_big_slot, N); DALLOC(c->big_mem, c->d_big_list, c->big_cap); DALLOC(g, c->d_big_count, 1);
-    DALLOC(g, c->d_seed_cnt, N); DALLOC(g, c->d_l_rep, N); DALLOC(g, c->d_status, N);
+    DALLOC(g, c->d_seed_cnt, N); DALLOC(g, c->d_l_rep, N); DALLOC(g, c->d_status, N); DALLOC(g, c->d_fin_list, N);
     {   // persistent-lane K1: 64 reads per wave in flight, as many waves as the device keeps resident (tunable for experiments)
         int want = c->co.smem_grid;
         i64 need = (c->cap_reads + 63) / 64;
@@ -491,6 +492,22 @@ static int k1_big_round(lh_context* c, const DOpts& o, const DIndex& ix4, int N,
     return LH_OK;
 }
 
+// the regular slots' intervals sorted, seed counts, l_rep: of the reads pass 3 listed (it has counted the others), or of every read
+static int smem_fin(lh_context* c, const DOpts& o, int N, bool listed) {
+    const int all = (N * 16 + 255) / 256;
+    LH_LAUNCH(k_smem_fin, listed && all > LH_FIN_GRID ? LH_FIN_GRID : all, 256, c->stream, o, N, c->d_intv, (const int32_t*)c->d_n_intv, c->d_seed_cnt, c->d_l_rep, (const int32_t*)c->d_big_slot,
+              (const int32_t*)(listed ? c->d_fin_list : nullptr), (const int32_t*)(listed ? &c->d_next_read->n_fin : nullptr));
+#ifdef LH_FIN_TRACE   // a development build's read-out (it waits for the stream): how many reads pass 3 listed
+    if (listed) {
+        int32_t n_fin = 0;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(&n_fin, &c->d_next_read->n_fin, sizeof n_fin, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[lh] k_smem_fin: %d of %d reads listed\n", (int)n_fin, N);
+    }
+#endif
+    return LH_OK;
+}
+
 // the batch's seed total and the reads that asked for a slot of the big slab, on the host (h_peek->k1)
 static int peek_seed_total(lh_context* c, int N) {
     LH_LAUNCH(k_peek_i64_i32, 1, 1, c->stream, (const i64*)(c->d_seed_off + N), (const int32_t*)&c->d_big_count->asked, &c->h_peek->k1.seeds);   // (not a copy-engine transfer: those may be busy with the previous result / the next batch)
@@ -550,15 +567,23 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         { int rc = k1_trace_lens(c, trace); if (rc) return rc; }
 #endif
         T_BEGIN("k_smem4_p3");
+        // pass 3 in lockstep is the last to touch a read's regular slots and walks them anyway: it counts the read's seeds and lists the few reads that need their
+        // intervals sorted in memory (k_smem_fin below); K2 ranks the others' inside its groups.  Every other path — no pass 3, the state machine's, the lane-per-seed
+        // K2, the trace build — keeps k_smem_fin over all reads
+        bool p3_counts = o.max_mem_intv > 0 && q4 && !(c->flags & LH_F_SEED_LANE);
+#ifdef LH_K1_TRACE
+        p3_counts = false;
+#endif
         if (o.max_mem_intv > 0 && q4)   // forward-only walks: one thread per read, in lockstep
-            LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr);
+            LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr,
+                      p3_counts ? c->d_seed_cnt : nullptr, p3_counts ? c->d_l_rep : nullptr, p3_counts ? c->d_fin_list : nullptr, p3_counts ? &c->d_next_read->n_fin : nullptr);
         else if (o.max_mem_intv > 0)
             smem_pass<3, false>(c, ix4, o, N, g3, nobig);
         T_END();
         T_BEGIN("k_smem_fin");
         // reads whose intervals outgrew their LH_MAX_INTV slots: the three passes again into the big slab (BWA's vectors grow: no read is refused)
         { int rc = k1_big_round(c, o, ix4, N, 0); if (rc) return rc; }
-        LH_LAUNCH(k_smem_fin, (N * 16 + 255) / 256, 256, c->stream, o, N, c->d_intv, c->d_n_intv, c->d_seed_cnt, c->d_l_rep, (const int32_t*)c->d_big_slot);
+        { int rc = smem_fin(c, o, N, p3_counts); if (rc) return rc; }
         T_END();
     }
     T_BEGIN("k_scan_seeds");
@@ -913,6 +938,12 @@ int lh_stage_dump_resident(lh_context* c, const lh_opts* opts, lh_stage_dump** o
     std::vector<DSeed> seeds;
     std::vector<DChain> chains;
     K1Big big; big.list = c->d_big_list; big.count = &c->d_big_count->listed; big.slot = c->d_big_slot; big.slab = c->d_big_slab; big.resume = nullptr;
+    {   // the dump shows a read's intervals sorted; the default path leaves that to K2's groups.  Seeds and chains are that path's: this sorts for the display only (and writes the same counts again)
+        DOpts o = to_dopts(opts);
+        o.wd = c->d_wd;
+        int rc = smem_fin(c, o, N, false);
+        if (rc) return rc;
+    }
     LH_LAUNCH(k_intv_rows, (N + 255) / 256, 256, c->stream, c->idx->d, N, c->d_intv, (const int32_t*)c->d_n_intv, big);   // K1 stores unique intervals by text position: the dump shows rows, like bwt_smem1a
     HIPCHK(hipStreamSynchronize(c->stream));
     D2H(n_intv, c->d_n_intv, N); D2H(intv, c->d_intv, (size_t)N * LH_MAX_INTV); D2H(seed_off, c->d_seed_off, N + 1); D2H(status, c->d_status, N);

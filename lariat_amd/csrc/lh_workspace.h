@@ -53,8 +53,9 @@ struct K1Counters {
     int32_t big_pass[3];   // the same for the second chance (k1_big_round)
     int32_t n_todo;        // reads k_smem_first left to pass 1: the length of lh_context::d_k1_todo
     int32_t n_p2_tasks;    // pass 2's tasks (k_p2_tasks): the length of lh_context::d_p2_tasks
+    int32_t n_fin;         // reads k_smem_p3_lock lists for k_smem_fin: the length of lh_context::d_fin_list
 };
-static_assert(sizeof(K1Counters) == 8 * sizeof(int32_t) && offsetof(K1Counters, big_pass) == 3 * sizeof(int32_t) && sizeof(K1Counters::big_pass) == 3 * sizeof(int32_t),
+static_assert(sizeof(K1Counters) == 9 * sizeof(int32_t) && offsetof(K1Counters, big_pass) == 3 * sizeof(int32_t) && sizeof(K1Counters::big_pass) == 3 * sizeof(int32_t),
               "the second chance's counters are cleared as one range");
 // k_big_collect addresses these two as count[0] and count[1]
 struct K1BigCounts {
