@@ -519,6 +519,20 @@ int lh_bgzf_timings(const lh_bgzf* z, double* upload_s, double* kernel_s, double
  * level of lh_bam_set_level has no meaning on the device path.  A failing device call fails the writer as a zlib error does: there is no silent fall-back.
  * z must outlive w or be taken off it first.  The end-of-file block and lh_bam_concat are the same on both paths. */
 int lh_bam_set_device(lh_bam_writer* w, lh_bgzf* z);
+/* on != 0: every later lh_bam_append derives and encodes its records on the compressor's device too (k_brec_plan, k_brec_write) and compresses them where they lie:
+ * the host gathers the at most four candidates a read's records read and uploads them with the ingest batch's text; the uncompressed BAM bytes never exist on the
+ * host, only the members and each file's last partial block come back.  The files are byte for byte those of host records + device compressor.  LH_E_ARG when no
+ * compressor is set; lh_bam_set_device(w, NULL) switches it off as well; both may be switched between appends.  LH_REC_DEBUG_TAGS stays a feature of the host
+ * path: an append with both set is LH_E_ARG and appends nothing.  A read name over 254 bytes, more than 65,535 CIGAR operations, or a molecule_difference that is
+ * not finite and below 2^31 (the device's %.6f of the DM tag) is LH_E_LIMIT, found before any byte is written: nothing is appended and the writer goes on.
+ * There is no fall-back: a failing device call fails the writer. */
+int lh_bam_set_device_records(lh_bam_writer* w, int32_t on);
+/* the last append on that path: host gather, upload, plan kernels (offsets included), write kernel, in seconds.  lh_bam_timings then reports records_s = their
+ * sum, join_s = 0, write_s = compression + download + fwrite */
+int lh_bam_records_timings(const lh_bam_writer* w, double out[4]);
+/* diagnostics: the device's printf("%.6f") (k_brec.h; the DM tag), n values -> 32 bytes each, NUL-terminated.  Exact for every finite |v| < 2^31: correctly rounded from
+ * the binary value, ties to even, as glibc prints.  Any other value: its 32 bytes are zero and the call returns LH_E_LIMIT.  LH_E_NODEVICE without a GPU. */
+int lh_diag_format_f6(int device, int32_t n, const double* v, char* out /* 32 bytes per value, NUL-terminated */);
 
 #ifdef __cplusplus
 }

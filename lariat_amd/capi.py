@@ -600,6 +600,14 @@ class Library:
         self.L.lh_records_free(txt)
         return out
 
+    def diag_format_f6(self, values, device=0):
+        """lh_diag_format_f6: the device's '%.6f' of every value -> list of str (LhError LH_E_LIMIT when one is refused)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        out = np.zeros(max(1, v.size) * 32, dtype=np.uint8)
+        self.L.lh_diag_format_f6.argtypes = [C.c_int, C.c_int32, C.c_void_p, C.c_void_p]
+        self.check(self.L.lh_diag_format_f6(int(device), int(v.size), v.ctypes.data if v.size else None, out.ctypes.data))
+        return [out[32 * i:32 * i + 32].tobytes().split(b"\0")[0].decode() for i in range(v.size)]
+
     def bam_concat(self, shard_dirs, out_dir):
         n = len(shard_dirs)
         dirs = (C.c_char_p * n)(*[d.encode() for d in shard_dirs])
@@ -940,6 +948,22 @@ class BamWriter:
         self.lib.check(self.lib.L.lh_bam_set_device(self.h, z.h if z is not None else None))
         self._z = z   # (the compressor must outlive its use by the writer)
 
+    def set_device_records(self, on=True):
+        """records appended from now on are derived and encoded on the compressor's device (lh_bam_set_device_records); needs set_device first"""
+        self.lib.L.lh_bam_set_device_records.argtypes = [C.c_void_p, C.c_int32]
+        self.lib.check(self.lib.L.lh_bam_set_device_records(self.h, 1 if on else 0))
+
+    def timings(self):
+        """the last append's phases (lh_bam_timings), and on the device record path lh_bam_records_timings' four"""
+        L = self.lib.L
+        L.lh_bam_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.lh_bam_records_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        r, j, wr = C.c_double(), C.c_double(), C.c_double()
+        self.lib.check(L.lh_bam_timings(self.h, C.byref(r), C.byref(j), C.byref(wr)))
+        t = (C.c_double * 4)()
+        self.lib.check(L.lh_bam_records_timings(self.h, t))
+        return {"records_s": r.value, "join_s": j.value, "write_s": wr.value, "gather_s": t[0], "upload_s": t[1], "plan_s": t[2], "encode_s": t[3]}
+
     def append(self, result, ingest_batch):
         rs = result.as_struct()
         self.lib.check(self.lib.L.lh_bam_append(self.h, C.byref(rs), ingest_batch.ptr))
@@ -999,4 +1023,5 @@ EXPORTED_SYMBOLS = [
     "lh_result_download", "lh_result_free", "lh_last_timings", "lh_last_rounds", "lh_stage_dump_resident", "lh_stage_dump_free", "lh_get_seq", "lh_device_memory", "lh_diag_gosort", "lh_diag_gosort_split", "lh_diag_bitonic", "lh_diag_introsort", "lh_diag_random_read", "lh_diag_valu_rate", "lh_diag_rescue_sw", "lh_diag_go_rand", "lh_diag_rescue_dedup",
     "lh_index_opts_init", "lh_context_opts_init", "lh_index_build_device", "lh_index_export", "lh_index_save", "lh_synth_genome", "lh_synth_reads", "lh_synth_write_fastq9", "lh_diag_index_check", "lh_batch_upload_slot", "lh_batch_select", "lh_bam_concat", "lh_reference_pack", "lh_index_set_holes", "lh_diag_index_digest", "lh_index_set_alt", "lh_index_alt", "lh_bam_set_level", "lh_bam_timings", "lh_result_download_begin", "lh_result_download_end", "lh_batch_stage_slot", "lh_host_alloc", "lh_host_free",
     "lh_bgzf_create", "lh_bgzf_free", "lh_bgzf_compress", "lh_bgzf_bound", "lh_bgzf_timings", "lh_bam_set_device",
+    "lh_bam_set_device_records", "lh_bam_records_timings", "lh_diag_format_f6",
 ]

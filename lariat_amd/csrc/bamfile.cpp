@@ -24,6 +24,7 @@ extern "C" int lh_set_error_(int code, const char* msg);
 // the device compressor's call for several inputs at once (lh_bgzf.inc)
 extern "C" int lh_bgzf_compress_segs_(lh_bgzf* z, int32_t n_seg, const uint8_t* const* seg, const int64_t* seg_len, uint8_t* out, int64_t out_cap, int64_t* out_len, int64_t* seg_off);
 #include "records_internal.h"
+#include "brec_internal.h"   // the device record encoder's call (lh_brec.inc)
 
 namespace {
 
@@ -89,6 +90,8 @@ struct lh_bam_writer {
     bool failed = false;
     lh_bgzf* dev = nullptr;   // lh_bam_set_device: the blocks are compressed there, not by zlib
     std::unique_ptr<uint8_t[]> zbuf; int64_t zbuf_cap = 0;   // the device path's members of one flush: kept between flushes, never cleared
+    bool dev_records = false;   // lh_bam_set_device_records: the records are derived and encoded on dev's device, not by records.cpp and encode()
+    double t_rec[4] = {0, 0, 0, 0};   // lh_bam_records_timings
 };
 
 namespace {
@@ -166,6 +169,26 @@ int encode(const lh_bam_writer* w, const LhRec& R, std::string& rec) {
     return b[ch < b.size() ? ch : b.size() - 1];
 }
 
+// the files' members, side by side from where they lie in the members' buffer (off: n files + 1 entries)
+bool write_members(lh_bam_writer* w, const uint8_t* z, const std::vector<int64_t>& off) {
+    const size_t n_out = w->outs.size();
+    std::atomic<size_t> next_out{0};
+    std::atomic<bool> all_ok{true};
+    auto write_out = [&]() {
+        for (size_t o = next_out++; o < n_out; o = next_out++) {
+            const size_t n = (size_t)(off[o + 1] - off[o]);
+            if (n && fwrite(z + off[o], 1, n, w->outs[o].f) != n) { all_ok = false; return; }
+        }
+    };
+    int wt = w->threads < 1 ? 1 : (w->threads > 16 ? 16 : w->threads);
+    if ((size_t)wt > n_out) wt = (int)n_out;
+    std::vector<std::thread> wth;
+    for (int t = 1; t < wt; ++t) wth.emplace_back(write_out);
+    write_out();
+    for (auto& t : wth) t.join();
+    return all_ok;
+}
+
 // the device path of flush: the complete blocks of all files (all bytes when `all`) go to the compressor in one call, a segment per file; the files are then
 // written side by side from where their members lie
 bool flush_device(lh_bam_writer* w, bool all) {
@@ -184,23 +207,36 @@ bool flush_device(lh_bam_writer* w, bool all) {
     const uint8_t* z = w->zbuf.get();
     int64_t z_len = 0;
     if (lh_bgzf_compress_segs_(w->dev, (int32_t)n_out, seg.data(), len.data(), w->zbuf.get(), w->zbuf_cap, &z_len, off.data())) return false;
-    std::atomic<size_t> next_out{0};
-    std::atomic<bool> all_ok{true};
-    auto write_out = [&]() {
-        for (size_t o = next_out++; o < n_out; o = next_out++) {
-            const size_t n = (size_t)(off[o + 1] - off[o]);
-            if (n && fwrite(z + off[o], 1, n, w->outs[o].f) != n) { all_ok = false; return; }
-        }
-    };
-    int wt = w->threads < 1 ? 1 : (w->threads > 16 ? 16 : w->threads);
-    if ((size_t)wt > n_out) wt = (int)n_out;
-    std::vector<std::thread> wth;
-    for (int t = 1; t < wt; ++t) wth.emplace_back(write_out);
-    write_out();
-    for (auto& t : wth) t.join();
-    if (!all_ok) { lh_set_error_(LH_E_IO, "write failed"); return false; }
+    if (!write_members(w, z, off)) { lh_set_error_(LH_E_IO, "write failed"); return false; }
     for (size_t o = 0; o < n_out; ++o) if (len[o]) w->outs[o].pending.erase(0, (size_t)len[o]);
     return true;
+}
+
+// lh_bam_append with the records made on the device (lh_bam_set_device_records): the encoder hands back every file's members and the bytes behind its last whole
+// block, which become its `pending` — the one carrier of state between appends on every path
+int append_device(lh_bam_writer* w, const lh_result* res, const lh_ingest_batch* in) {
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    if (w->rec_flags & LH_REC_DEBUG_TAGS)
+        return lh_set_error_(LH_E_ARG, "lh_bam_append: the debug tags (LH_REC_DEBUG_TAGS) are a feature of the host record path: not with lh_bam_set_device_records; nothing was appended");
+    const double t0 = now();
+    LhBrecCall c;
+    c.res = res; c.in = in; c.names = &w->names; c.bucket = &w->bucket; c.chunk = w->chunk; c.threads = w->threads;
+    for (Out& o : w->outs) c.pending.push_back(&o.pending);
+    c.zbuf = &w->zbuf; c.zbuf_cap = &w->zbuf_cap;
+    const int rc = lh_brec_encode_(w->dev, &c);
+    if (rc == LH_E_LIMIT || rc == LH_E_ARG) return rc;   // the batch was turned away before a byte was written: the writer goes on
+    if (rc) {
+        w->failed = true;
+        const std::string why = std::string("lh_bam_append: encoding or compression on the device failed: ") + lh_last_error();
+        return lh_set_error_(LH_E_IO, why.c_str());
+    }
+    const double t1 = now();
+    if (!write_members(w, w->zbuf.get(), c.seg_off)) { w->failed = true; return lh_set_error_(LH_E_IO, "lh_bam_append: write failed"); }
+    for (size_t o = 0; o < w->outs.size(); ++o) w->outs[o].pending.swap(c.rest[o]);
+    for (int k = 0; k < 4; ++k) w->t_rec[k] = c.t[k];
+    const double t_enc = c.t[0] + c.t[1] + c.t[2] + c.t[3];
+    w->t_records = t_enc < t1 - t0 ? t_enc : t1 - t0; w->t_join = 0; w->t_write = now() - t0 - w->t_records;
+    return LH_OK;
 }
 
 // compresses and writes every complete block of every file (all of it when `all`), blocks in parallel
@@ -321,6 +357,18 @@ extern "C" int lh_bam_set_level(lh_bam_writer* w, int32_t level) {
 extern "C" int lh_bam_set_device(lh_bam_writer* w, lh_bgzf* z) {
     if (!w) return lh_set_error_(LH_E_ARG, "lh_bam_set_device: null writer");
     w->dev = z;
+    if (!z) w->dev_records = false;
+    return LH_OK;
+}
+extern "C" int lh_bam_set_device_records(lh_bam_writer* w, int32_t on) {
+    if (!w) return lh_set_error_(LH_E_ARG, "lh_bam_set_device_records: null writer");
+    if (on && !w->dev) return lh_set_error_(LH_E_ARG, "lh_bam_set_device_records: the writer has no device compressor (lh_bam_set_device): the records are encoded on its device");
+    w->dev_records = on != 0;
+    return LH_OK;
+}
+extern "C" int lh_bam_records_timings(const lh_bam_writer* w, double out[4]) {
+    if (!w || !out) return lh_set_error_(LH_E_ARG, "lh_bam_records_timings: null argument");
+    for (int k = 0; k < 4; ++k) out[k] = w->t_rec[k];
     return LH_OK;
 }
 extern "C" int lh_bam_timings(const lh_bam_writer* w, double* records_s, double* join_s, double* write_s) {
@@ -332,6 +380,7 @@ extern "C" int lh_bam_timings(const lh_bam_writer* w, double* records_s, double*
 }
 extern "C" int lh_bam_append(lh_bam_writer* w, const lh_result* res, const lh_ingest_batch* in) {
     if (!w || !res || !in) return lh_set_error_(LH_E_ARG, "lh_bam_append: null argument");
+    if (w->dev && w->dev_records) return append_device(w, res, in);
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now();
     std::vector<const char*> names;

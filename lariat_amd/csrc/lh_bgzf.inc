@@ -9,6 +9,9 @@
 #define LH_BGZF_DEFAULT_BLOCKS 2048   // a launch of that many waves fills the device: 8 single-wave workgroups per CU (the kernel's LDS and registers) on 256 CUs
 #define LH_BGZF_MAX_WAVES 2048   // waves of one launch (each owns a token scratch of LH_BGZF_DATA words); more blocks: a wave takes several
 
+struct lh_brec_bufs;                       // the record encoder's buffers (lh_brec.inc): created by its first use, freed with the compressor
+static void brec_free(lh_brec_bufs* b);
+
 struct lh_bgzf {
     int device = 0, max_blocks = 0, waves = 0;
     std::mutex mu;
@@ -25,7 +28,9 @@ struct lh_bgzf {
     uint32_t* d_consts = nullptr;
     DevGroup mem;   // every device buffer of the compressor
     double t_up = 0, t_kernel = 0, t_down = 0;   // the last lh_bgzf_compress's phases, seconds (device time, summed over its chunks)
+    lh_brec_bufs* enc = nullptr;
     ~lh_bgzf() {
+        brec_free(enc);
         for (Set& s : set) {
             if (s.st) { (void)hipStreamSynchronize(s.st); (void)hipStreamDestroy(s.st); }
             for (hipEvent_t e : s.ev) if (e) (void)hipEventDestroy(e);

@@ -995,3 +995,4 @@ void lh_stage_dump_free(lh_stage_dump* d) { if (d) delete (DumpArenaH*)d->arena_
 #include "lh_lanes.inc"
 
 #include "lh_bgzf.inc"   // the device compressor of BGZF members (lh_bgzf_*), an object of its own
+#include "lh_brec.inc"   // the device encoder of BAM records (lh_bam_set_device_records), on the compressor's device

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""lh_bam_append on one aligned batch by three paths: the host writer at zlib's default level, the host writer at level 1, the device writer (lh_bam_set_device).
-Per path: lh_bam_timings' phases, pairs/s, compressed against uncompressed bytes; for the device path lh_bgzf_timings too.  Then what the compressor costs an align loop that runs
-beside it: lh_bgzf_compress in a loop on a second thread for the whole of the align loop's measurement.
+"""lh_bam_append on one aligned batch by four paths: the host writer at zlib's default level, the host writer at level 1, the device writer (lh_bam_set_device: host
+records, device compressor) and the device writer with the records made on the device too (lh_bam_set_device_records).
+Per path: lh_bam_timings' phases, pairs/s, compressed against uncompressed bytes; for the device paths lh_bgzf_timings too, for the last lh_bam_records_timings and the rate of
+k_brec_write; the two device paths' files are compared byte for byte.  Then (unless `writer-only`) what the compressor costs an align loop that runs beside it:
+lh_bgzf_compress in a loop on a second thread for the whole of the align loop's measurement.
 
-usage: bam_device_probe.py [genome Mb = 100] [barcodes of 100 pairs = 5000] [host threads = 16]"""
+usage: bam_device_probe.py [genome Mb = 100] [barcodes of 100 pairs = 5000] [host threads = 16] [writer-only]"""
 import ctypes as C
+import hashlib
 import os
 import shutil
 import struct
@@ -53,7 +56,15 @@ def sizes(out):
     return comp, unc
 
 
-def one(tag, level=None, z=None, keep=False):
+def digest(out):
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(out)):
+        h.update(f.encode())
+        h.update(open(os.path.join(out, f), "rb").read())
+    return h.hexdigest()
+
+
+def one(tag, level=None, z=None, records=False):
     out = os.path.join(d, tag)
     os.makedirs(out)
     w = lib.bam_writer(out, names, lens, threads=threads)
@@ -61,18 +72,21 @@ def one(tag, level=None, z=None, keep=False):
         lib.L.lh_bam_set_level(w.h, level)
     if z is not None:
         w.set_device(z)
+        w.set_device_records(records)
     t0 = time.time()
     w.append(res, b)
     ta = time.time() - t0
     x, y, t = C.c_double(), C.c_double(), C.c_double()
     lib.L.lh_bam_timings(w.h, C.byref(x), C.byref(y), C.byref(t))
+    rt = w.timings() if records else None
     zt = z.timings() if z is not None else None
     t0 = time.time()
     w.close()
     tc = time.time() - t0
     comp, unc = sizes(out)
+    sha = digest(out) if z is not None else None
     shutil.rmtree(out)
-    return dict(append=ta, close=tc, records=x.value, join=y.value, write=t.value, comp=comp, unc=unc, zt=zt)
+    return dict(append=ta, close=tc, records=x.value, join=y.value, write=t.value, comp=comp, unc=unc, zt=zt, rt=rt, sha=sha)
 
 
 def show(tag, m):
@@ -81,14 +95,27 @@ def show(tag, m):
     if m["zt"]:
         print("%-22s lh_bgzf_timings of the append's call: upload %.3f s, kernel %.3f s, download %.3f s (device time, chunks overlap)"
               % ("", m["zt"]["upload_s"], m["zt"]["kernel_s"], m["zt"]["download_s"]))
+    if m["rt"]:   # every record is written twice (bc_sorted and its bucket): k_brec_write stores 2 x the uncompressed record bytes
+        print("%-22s lh_bam_records_timings: gather %.3f s (host), upload %.3f s, plan kernels %.3f s, write kernel %.3f s = %.1f GB/s of BAM bytes stored"
+              % ("", m["rt"]["gather_s"], m["rt"]["upload_s"], m["rt"]["plan_s"], m["rt"]["encode_s"], m["unc"] / max(m["rt"]["encode_s"], 1e-9) / 1e9))
 
 
 z = lib.bgzf()
 one("warm", z=z)   # first use: page-locked staging is touched, the kernel's code is loaded
+one("warmr", z=z, records=True)   # ... and the encoder's buffers are allocated
 for rep in range(2):
     show("host, default level:", one("h%d" % rep))
     show("host, level 1:", one("l%d" % rep, level=1))
-    show("device:", one("d%d" % rep, z=z))
+    md = one("d%d" % rep, z=z)
+    show("device:", md)
+    mr = one("r%d" % rep, z=z, records=True)
+    show("device, records too:", mr)
+    print("%-22s the two device paths' files are %s" % ("", "EQUAL byte for byte" if md["sha"] == mr["sha"] else "DIFFERENT"))
+    print("%-22s append: %.3f s against %.3f s (%.2f x)" % ("", mr["append"], md["append"], md["append"] / mr["append"]))
+if len(sys.argv) > 4 and sys.argv[4] == "writer-only":
+    z.close()
+    shutil.rmtree(d, ignore_errors=True)
+    sys.exit(0)
 
 # the align loop alone, then beside a thread that keeps the compressor busy: lh_bgzf_compress in a loop on the BAM bytes of this batch, so that k_bgzf and its
 # transfers are in flight for the whole of the align loop's measurement (a writer thread would spend a third of its time encoding records on the host)
