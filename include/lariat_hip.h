@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LH_ABI_VERSION 7
+#define LH_ABI_VERSION 8
 
 /* status codes */
 #define LH_OK 0
@@ -81,6 +81,7 @@ typedef struct lh_opts {
 #define LH_F_P2_TASKS 128u       /* K1 pass 2: a read's re-seeding calls shared by up to four lanes whatever the previous batch looked like (default: only after a repeat-rich batch) */
 #define LH_F_RESCUE_FULL 256u     /* K6: every mate-rescue Smith-Waterman runs all rows of its window (default: the rows k_resc_cert proves sufficient, k_rescue3.h) */
 #define LH_F_SEED_LANE 512u       /* (ABI 7) K2: one lane per seed after a pass that names every seed slot's read (k_seed_owner + k_seed) and k_smem_fin sorting every read's intervals in memory before it; default: a 16-lane group per read that ranks its intervals itself, k_seed_grp */
+#define LH_F_TAIL_PASSES 1024u    /* (ABI 8) K5's lane form as a pass over every read after K4 (k_dedup_fast) and K8's prologue (k_rfa_init, k_rfa_order) after K7 on the main stream; default: a read's K5 on the lane that finishes its extension, the prologue beside K7 */
 #define LH_F_CHAIN_WAVE 64u      /* K3: the reads a lane does not chain all go to the wave-per-seed kernel (k_chain), none to the cluster kernel (k_chain_cl) */
 
 /* how an index is made resident (lh_index_load / lh_index_from_arrays / lh_index_build_device); NULL = defaults */

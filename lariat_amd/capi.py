@@ -13,11 +13,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LARIAT_HIP_LIB") or os.path.join(_HERE, "_build", "liblariat_hip.so")
 
 LH_OK = 0
-LH_ABI_VERSION = 7
+LH_ABI_VERSION = 8
 LH_E_ARG, LH_E_IO, LH_E_HIP, LH_E_CAPACITY, LH_E_NODEVICE, LH_E_LIMIT = 1, 2, 3, 4, 5, 6
 # lh_opts.flags
 LH_REC_DEBUG_TAGS = 1
-LH_F_NO_SWEEP_FILTER, LH_F_EXT_WAVE, LH_F_EXT_SERIAL, LH_F_CHAIN_WAVE, LH_F_P2_TASKS, LH_F_RESCUE_FULL, LH_F_SEED_LANE = 1, 16, 32, 64, 128, 256, 512
+LH_F_NO_SWEEP_FILTER, LH_F_EXT_WAVE, LH_F_EXT_SERIAL, LH_F_CHAIN_WAVE, LH_F_P2_TASKS, LH_F_RESCUE_FULL, LH_F_SEED_LANE, LH_F_TAIL_PASSES = 1, 16, 32, 64, 128, 256, 512, 1024
 LH_MAX_READ_LEN = 250
 
 c_i32p = C.POINTER(C.c_int32)

@@ -62,10 +62,11 @@ __global__ void __launch_bounds__(64, LH_CHAIN_LANE_WAVES) k_chain_lane(DIndex i
     const i64* __restrict__ seq_off = A.seq_off; const i64* __restrict__ seed_off = A.seed_off; int32_t* __restrict__ sdone = A.sdone;
     __shared__ uint32_t cl[LH_CHAIN_LANE_MAXC * 8 * 64];
     const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
-    int heavy = 0, ext_out = 0, ext_key = 0;
+    int heavy = 0, ext_out = 0, ext_key = 0, dd_need = 0;
     u64 win = 0, cells = 0;
     int nch_done = 0;
     if (r < n_reads) {
+        if (A.dd_done) A.dd_done[r] = 0;   // (every read's mark starts here; ext_control sets it where the read finishes, below or in a later round)
         const i64 base = seed_off[r];
         const int S = (int)(seed_off[r + 1] - base);
         if (seed_off[r + 1] > pool_cap) { n_chains[r] = 0; A.n_regs[r] = 0; atomicOr(&status[r], LH_ST_POOL_OVERFLOW); }
@@ -274,11 +275,12 @@ __global__ void __launch_bounds__(64, LH_CHAIN_LANE_WAVES) k_chain_lane(DIndex i
                 }
                 nch_done = m;
             }
-            if (fuse) ext_out = ext_control<false>(ix, o, A, r, nullptr, lane, &ext_key, &cells);
+            if (fuse) ext_out = ext_control<false>(ix, o, A, r, nullptr, lane, &ext_key, &cells, &dd_need);
             }
         }
     }
     ext_append(ext_out, r, ext_key, lane, next_count, next_list, next_key, defer_count, defer_list);
+    if (A.dd_done) dedup_need_append(dd_need, r, lane, A.dd_list, A.dd_count);
     if (ctr) {
         unsigned w32 = (unsigned)win;   // < 2^32 window bases per read
         u64 wtot = (u64)(uint32_t)wave_sum_i32((int)(w32 >> 16)) << 16;

@@ -222,80 +222,93 @@ __device__ __forceinline__ int dev_patch_needs_dp(const DIndex& ix, const DOpts&
     } else if (w > o.w << 2 || r >= LH_PATCH_MAX_R_BW * 2) return 0;
     return 1;
 }
-__global__ void __launch_bounds__(256) k_dedup_fast(DIndex ix, DOpts o, int n_reads, const i64* __restrict__ reg_off, DReg* __restrict__ regs, int32_t* __restrict__ n_regs,
-                                                     int32_t* __restrict__ best_score, int32_t* __restrict__ list, int32_t* __restrict__ list_count, uint8_t* __restrict__ clean) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
+// K5 for one read by one lane: n = the read's regions as K4 left them (n_regs[r]).  Returns 1 if the read is the wave kernel's (k_dedup): nothing of it has been
+// touched then.  The lane that wrote the read's last region calls this where the read's extension ends (ext_control, k_extend2.h: its own stores to the records
+// precede these loads in program order); k_dedup_fast calls it for the reads that finish elsewhere.
+__device__ __forceinline__ int dev_dedup_fast_read(const DIndex& ix, const DOpts& o, int r, int n, const i64* reg_off, DReg* regs, int32_t* n_regs, int32_t* best_score,
+                                                   uint8_t* clean) {
     int need = 0;
-    if (r < n_reads) {
-        int n = n_regs[r];
-        clean[r] = 1;   // (nothing to compare, or two regions that were — unless they end at the same position, below; a listed read: k_dedup's word)
-        if (n <= 1) best_score[r] = n == 1 ? regs[reg_off[r]].score : 0;
-        else if (n == 2) {
-            // (the decisions read six fields of each record; the records themselves move at most once, as 8-byte words: whole-record
-            // selects made the compiler keep them in 376 B of scratch)
-            DReg* av = regs + reg_off[r];
-            const i64 rb0 = av[0].rb, re0 = av[0].re, rb1 = av[1].rb, re1 = av[1].re;
-            const int qb0 = av[0].qb, qe0 = av[0].qe, sc0 = av[0].score, rid0 = av[0].rid, qb1 = av[1].qb, qe1 = av[1].qe, sc1 = av[1].score, rid1 = av[1].rid;
-            // sorted by re (klib's introsort on two elements: swapped only when strictly out of order): qq = the first, p = the second
-            const int s = re1 < re0;
-            const i64 q_rb = s ? rb1 : rb0, q_re = s ? re1 : re0, p_rb = s ? rb0 : rb1, p_re = s ? re0 : re1;
-            const int q_qb = s ? qb1 : qb0, q_qe = s ? qe1 : qe0, q_sc = s ? sc1 : sc0, q_rid = s ? rid1 : rid0;
-            const int p_qb = s ? qb0 : qb1, p_qe = s ? qe0 : qe1, p_sc = s ? sc0 : sc1, p_rid = s ? rid0 : rid1;
-            int kp = p_qe > p_qb, kq = q_qe > q_qb;   // still there
-            if (p_rid == q_rid && p_rb < q_re + o.max_chain_gap) {
-                const i64 orr = q_re - p_rb;
-                const i64 oq = q_qb < p_qb ? q_qe - p_qb : p_qe - q_qb;
-                const i64 mr = q_re - q_rb < p_re - p_rb ? q_re - q_rb : p_re - p_rb;
-                const i64 mq = q_qe - q_qb < p_qe - p_qb ? q_qe - q_qb : p_qe - p_qb;
-                if ((float)orr > o.mask_level_redun * (float)mr && (float)oq > o.mask_level_redun * (float)mq) {
-                    if (p_sc < q_sc) kp = 0;
-                    else kq = 0;
-                } else if (q_rb < p_rb) {
-                    DReg a, b;   // (mem_patch_reg's tests up to its DP read the spans only)
-                    a.rb = q_rb; a.re = q_re; a.qb = q_qb; a.qe = q_qe; b.rb = p_rb; b.re = p_re; b.qb = p_qb; b.qe = p_qe;
-                    need = dev_patch_needs_dp(ix, o, a, b);
+    clean[r] = 1;   // (nothing to compare, or two regions that were — unless they end at the same position, below; a listed read: k_dedup's word)
+    if (n <= 1) best_score[r] = n == 1 ? regs[reg_off[r]].score : 0;
+    else if (n == 2) {
+        // (the decisions read six fields of each record; the records themselves move at most once, as 8-byte words: whole-record
+        // selects made the compiler keep them in 376 B of scratch)
+        DReg* av = regs + reg_off[r];
+        const i64 rb0 = av[0].rb, re0 = av[0].re, rb1 = av[1].rb, re1 = av[1].re;
+        const int qb0 = av[0].qb, qe0 = av[0].qe, sc0 = av[0].score, rid0 = av[0].rid, qb1 = av[1].qb, qe1 = av[1].qe, sc1 = av[1].score, rid1 = av[1].rid;
+        // sorted by re (klib's introsort on two elements: swapped only when strictly out of order): qq = the first, p = the second
+        const int s = re1 < re0;
+        const i64 q_rb = s ? rb1 : rb0, q_re = s ? re1 : re0, p_rb = s ? rb0 : rb1, p_re = s ? re0 : re1;
+        const int q_qb = s ? qb1 : qb0, q_qe = s ? qe1 : qe0, q_sc = s ? sc1 : sc0, q_rid = s ? rid1 : rid0;
+        const int p_qb = s ? qb0 : qb1, p_qe = s ? qe0 : qe1, p_sc = s ? sc0 : sc1, p_rid = s ? rid0 : rid1;
+        int kp = p_qe > p_qb, kq = q_qe > q_qb;   // still there
+        if (p_rid == q_rid && p_rb < q_re + o.max_chain_gap) {
+            const i64 orr = q_re - p_rb;
+            const i64 oq = q_qb < p_qb ? q_qe - p_qb : p_qe - q_qb;
+            const i64 mr = q_re - q_rb < p_re - p_rb ? q_re - q_rb : p_re - p_rb;
+            const i64 mq = q_qe - q_qb < p_qe - p_qb ? q_qe - q_qb : p_qe - p_qb;
+            if ((float)orr > o.mask_level_redun * (float)mr && (float)oq > o.mask_level_redun * (float)mq) {
+                if (p_sc < q_sc) kp = 0;
+                else kq = 0;
+            } else if (q_rb < p_rb) {
+                DReg a, b;   // (mem_patch_reg's tests up to its DP read the spans only)
+                a.rb = q_rb; a.re = q_re; a.qb = q_qb; a.qe = q_qe; b.rb = p_rb; b.re = p_re; b.qb = p_qb; b.qe = p_qe;
+                need = dev_patch_needs_dp(ix, o, a, b);
+            }
+        }
+        if (!need) {
+            // exclude, sort by (score desc, rb, qb), drop an identical hit
+            int m = 0, first = 0;   // first: the record (0 / 1) that ends up in front
+            if (kq && kp) {   // order after the first sort: qq, p
+                const bool p_first = p_sc > q_sc || (p_sc == q_sc && (p_rb < q_rb || (p_rb == q_rb && p_qb < q_qb)));
+                first = p_first ? 1 - s : s;
+                m = (p_sc == q_sc && p_rb == q_rb && p_qb == q_qb) ? 1 : 2;
+            } else if (kq) { first = s; m = 1; }
+            else if (kp) { first = 1 - s; m = 1; }
+            if (m >= 1 && first == 1) {   // the records change places (or the second one moves to the front)
+                constexpr int NW = (int)(sizeof(DReg) / 8);
+                static_assert(sizeof(DReg) % 8 == 0, "a region record is a whole number of 8-byte words");
+                u64* w0 = (u64*)&av[0];
+                u64* w1 = (u64*)&av[1];
+                u64 a[NW], b[NW];
+#pragma unroll
+                for (int k = 0; k < NW; ++k) { a[k] = w0[k]; b[k] = w1[k]; }
+#pragma unroll
+                for (int k = 0; k < NW; ++k) w0[k] = b[k];
+                if (m == 2) {
+#pragma unroll
+                    for (int k = 0; k < NW; ++k) w1[k] = a[k];
                 }
             }
-            if (!need) {
-                // exclude, sort by (score desc, rb, qb), drop an identical hit
-                int m = 0, first = 0;   // first: the record (0 / 1) that ends up in front
-                if (kq && kp) {   // order after the first sort: qq, p
-                    const bool p_first = p_sc > q_sc || (p_sc == q_sc && (p_rb < q_rb || (p_rb == q_rb && p_qb < q_qb)));
-                    first = p_first ? 1 - s : s;
-                    m = (p_sc == q_sc && p_rb == q_rb && p_qb == q_qb) ? 1 : 2;
-                } else if (kq) { first = s; m = 1; }
-                else if (kp) { first = 1 - s; m = 1; }
-                if (m >= 1 && first == 1) {   // the records change places (or the second one moves to the front)
-                    constexpr int NW = (int)(sizeof(DReg) / 8);
-                    static_assert(sizeof(DReg) % 8 == 0, "a region record is a whole number of 8-byte words");
-                    u64* w0 = (u64*)&av[0];
-                    u64* w1 = (u64*)&av[1];
-                    u64 a[NW], b[NW];
-#pragma unroll
-                    for (int k = 0; k < NW; ++k) { a[k] = w0[k]; b[k] = w1[k]; }
-#pragma unroll
-                    for (int k = 0; k < NW; ++k) w0[k] = b[k];
-                    if (m == 2) {
-#pragma unroll
-                        for (int k = 0; k < NW; ++k) w1[k] = a[k];
-                    }
-                }
-                if (m >= 1) av[0].n_comp = 1;
-                if (m == 2) av[1].n_comp = 1;
-                n_regs[r] = m;
-                if (m == 2 && re0 == re1) clean[r] = 0;
-                const int f_sc = first ? sc1 : sc0, o_sc = first ? sc0 : sc1;
-                best_score[r] = m == 0 ? 0 : (m == 2 && o_sc > f_sc ? o_sc : f_sc);
-            }
-        } else need = 1;
-    }
-    u64 m = __ballot(need);
+            if (m >= 1) av[0].n_comp = 1;
+            if (m == 2) av[1].n_comp = 1;
+            n_regs[r] = m;
+            if (m == 2 && re0 == re1) clean[r] = 0;
+            const int f_sc = first ? sc1 : sc0, o_sc = first ? sc0 : sc1;
+            best_score[r] = m == 0 ? 0 : (m == 2 && o_sc > f_sc ? o_sc : f_sc);
+        }
+    } else need = 1;
+    return need;
+}
+// wave-wide: the lanes whose read is the wave kernel's append it to k_dedup's list
+__device__ __forceinline__ void dedup_need_append(int need, int r, int lane, int32_t* list, int32_t* list_count) {
+    const u64 m = __ballot(need);
     if (m) {
         int basep = 0;
         if (lane == 0) basep = atomicAdd(list_count, (int32_t)__popcll(m));
         basep = wave_readlane(basep, 0);
         if (need) list[basep + lanes_below(m, lane)] = r;
     }
+}
+// K5, lane per read, for the reads that did not finish on a lane of K4 — done[r] == 0: the wave-extended reads, a read whose seeds overflowed their pool, every
+// read under LH_F_EXT_WAVE — or for every read (done == null: LH_F_TAIL_PASSES).  A read that is done is not touched: K6 may not have started, but its records are final
+__global__ void __launch_bounds__(256) k_dedup_fast(DIndex ix, DOpts o, int n_reads, const i64* __restrict__ reg_off, DReg* __restrict__ regs, int32_t* __restrict__ n_regs,
+                                                     int32_t* __restrict__ best_score, int32_t* __restrict__ list, int32_t* __restrict__ list_count, uint8_t* __restrict__ clean,
+                                                     const uint8_t* __restrict__ done) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
+    int need = 0;
+    if (r < n_reads && !(done && done[r])) need = dev_dedup_fast_read(ix, o, r, n_regs[r], reg_off, regs, n_regs, best_score, clean);
+    dedup_need_append(need, r, lane, list, list_count);
 }
 
 // K5, wave per listed read (list == null: every read).  Also records the best pre-rescue score of the read (gobwa.go:264-283).

@@ -12,6 +12,7 @@
 //   - the DPs of different reads run side by side only when they have the same shape: see "K4 as ROUNDS" below.
 #pragma once
 #include "k_extend.h"
+#include "k_dedup.h"   // dev_dedup_fast_read: K5 for a read, where its extension ends
 
 #define EH_H(v) ((int)((v) & 0xffffu))
 #define EH_E(v) ((int)(((v) >> 16) & 0x1fffu))
@@ -242,6 +243,7 @@ struct DExtJobs {
     int32_t next[LH_EXT_ROUNDS + 2];          // round k's slice counter: its waves take slices of 64 jobs in the sorted order (heaviest bins first)
     int32_t kinds[3 * (LH_EXT_ROUNDS + 2)];   // diagnostics: narrow / live-interval / short full-band jobs of round k
     int32_t wnext;                            // (the long queue) k_ext_wround's next call
+    int32_t dd_need;                          // reads K5's lane form leaves to k_dedup (ExtArgs::dd_list): cleared with the block before K3, appended to from round 0 on
     int32_t wave_range[2], heavy_range[2], defer_range[2];   // [0, n): the reads the wave kernels chain and extend (k_chain_lane's list); the reads round 0 / the later rounds left to the wave extension kernel
 };
 // job key: bins 0..959 = narrow band in the circular window (same w: same cells per row), 960..1215 = full band in the live-interval window, 1216..1471 = full band, fewer than 64 columns
@@ -316,18 +318,24 @@ struct ExtArgs {   // what a read's control flow reads and writes
     const int32_t* sorder; int32_t* sdone; const i64* chain_rmax; const i64* reg_off; DReg* regs; int32_t* n_regs; ExtSt* est;
     // the long queue's units (one chain of a read each, indexed like the chain: seed_off[read] + chain): owner read, saved state, regions found; per read: "extend me from scratch"
     const int32_t* u_read; ExtSt* est_u; int32_t* nreg_u; int32_t* rflag;
+    // K5 where a read finishes on a lane (dev_dedup_fast_read, k_dedup.h): its outputs, the per-read mark "K5 is done" (null: K5 as a pass of its own, LH_F_TAIL_PASSES
+    // and LH_F_EXT_WAVE) and the list of the reads that need the wave kernel, k_dedup
+    int32_t* dd_best; uint8_t* dd_clean; uint8_t* dd_done; int32_t* dd_list; int32_t* dd_count;
 };
 // mem_chain2aln for read r, from the start (DP = false) or from its queued ksw_extend2 call (DP = true: the call is made here, in
 // the lane's LDS window ehl), up to the next call that needs a DP.  Returns 0: the read is finished (n_regs written); 1: a call was
 // queued (state saved, *key = its bin); 2: the read is left to the wave-per-read kernel (a live-interval window outgrew its 64 columns,
 // or — first seed of the read only, as before — a long side whose diagonal loses LH_NARROW_MAX_LOSS or more, e.g. behind an indel:
 // one full-band DP of that size keeps a lane busy for most of a millisecond).
+// A read that finishes here (not a UNIT) gets its K5 at once while A.dd_done is set (dev_dedup_fast_read on the records this lane has just written); *dd_need = 1
+// then says that the read is the wave kernel's: the caller appends it to k_dedup's list, wave-wide (dedup_need_append).
 // UNIT (the long queue, below): id names ONE chain of a read — the program runs that chain alone, its regions go to the chain's own slots
 // (region slot = seed slot: a chain yields at most one region per seed), and the test against earlier regions only sees the chain's own.
 // WAVE (UNIT only; k_ext_wround): all 64 lanes run the unit's program in step, and its pending call — one whose live interval outgrew a lane's
 // 64-column window — is made by the whole wave (wave_ksw_extend2, k_extend.h: ehl = the read's bytes in LDS); the unit then goes back to the lanes' queue.
 template <bool DP, bool UNIT = false, bool WAVE = false>
-__device__ __forceinline__ int ext_control(const DIndex& ix, const DOpts& o, const ExtArgs& A, const int id, uint32_t* ehl, const int lane, int* key_out, u64* cells_out) {
+__device__ __forceinline__ int ext_control(const DIndex& ix, const DOpts& o, const ExtArgs& A, const int id, uint32_t* ehl, const int lane, int* key_out, u64* cells_out,
+                                           int* dd_need = nullptr) {
     const int r = UNIT ? A.u_read[id] : id;
     const uint8_t* seq = A.seq; const uint32_t* q4 = A.q4; const i64* seq_off = A.seq_off; const i64* seed_off = A.seed_off; const DChain* chains = A.chains;
     const DSeed* cseeds = A.cseeds; const int32_t* n_chains = A.n_chains; const int32_t* sorder = A.sorder; int32_t* sdone = A.sdone; const i64* chain_rmax = A.chain_rmax;
@@ -512,7 +520,13 @@ __device__ __forceinline__ int ext_control(const DIndex& ix, const DOpts& o, con
             if (!out) ++ci;
         }
         // (UNIT, verdict 2 = the pending call's live interval outgrew the lane's window: the saved state still describes that call; the unit is listed for k_ext_wround)
-        if (!out) { if (UNIT) A.nreg_u[id] = n_av; else n_regs[r] = n_av; }
+        if (!out) {
+            if (UNIT) A.nreg_u[id] = n_av;
+            else {
+                n_regs[r] = n_av;
+                if (A.dd_done) { *dd_need = dev_dedup_fast_read(ix, o, r, n_av, reg_off, regs, n_regs, A.dd_best, A.dd_clean); A.dd_done[r] = 1; }
+            }
+        }
         else if (out == 1) {
             ExtSt st;
             st.w0 = k | side << 24 | tri << 25 | (aw0 != o.w ? 1 : 0) << 26; st.narrow = narrow; st.sc0 = sc0; st.w1 = ci | n_av << 16;
@@ -561,9 +575,10 @@ __global__ void __launch_bounds__(64) k_ext_round(DIndex ix, DOpts o, const int3
         if (first + blk * 64 >= last) break;
         const int g = first + blk * 64 + lane;
         const int r = g < last ? order[g] : -1;
-        int out = 0, key = 0;
-        if (r >= 0) out = ext_control<true, UNIT>(ix, o, A, r, ehl, lane, &key, &cells);
+        int out = 0, key = 0, dd_need = 0;
+        if (r >= 0) out = ext_control<true, UNIT>(ix, o, A, r, ehl, lane, &key, &cells, &dd_need);
         ext_append(out, r, key, lane, next_count, next_list, next_key, defer_count, defer_list);
+        if (!UNIT && A.dd_done) dedup_need_append(dd_need, r, lane, A.dd_list, A.dd_count);
     }
     if (ctr) {
         uint32_t lo = (uint32_t)cells;   // < 2^32 cells per lane

@@ -21,7 +21,7 @@ struct DInf {   // per-candidate / per-read inference outputs (device)
     int32_t *molecule_id, *mapq;
     double *mol_diff, *mol_conf, *sum_move;
     i64* mate;          // global candidate index or -1
-    int32_t* cand_read; // global read index of the candidate (filled by k_rfa's init)
+    int32_t* cand_read; // global read index of the candidate (filled by k_aln_prep, k_aln.h)
     // per read
     i64 *active_idx, *second_best_idx, *split_idx;
     double *second_best_score, *as_score, *split_second_best, *split_score;
@@ -340,7 +340,8 @@ static_assert(24 * LH_RFA_MQ_CHUNK <= LH_RFA_LDS_BYTES, "mate staging of estimat
 // split reads, which read what estimateMapQualities leaves for EVERY read of the barcode, follow in k_rfa_post.  Scratch of the wave kernels: the slabs
 // of the barcode program, free while they run.
 __global__ void __launch_bounds__(256) k_rfa_init(int n_reads, DCand R, DInf S, i64 cand_cap) {
-    // Alignment defaults, lariat.go:1655-1689 (S.cand_read was written by k_aln_prep)
+    // Alignment defaults, lariat.go:1655-1689.  Reads cand_off and writes only DInf columns no kernel of K7 touches, so it runs beside K7 (S.cand_read, which
+    // k_aln_flat reads, is k_aln_prep's; k_rfa_tag completes it)
     const i64 n_cand = R.cand_off[n_reads] < cand_cap ? R.cand_off[n_reads] : cand_cap;
     for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < n_cand; g += (i64)gridDim.x * blockDim.x) {
         S.active[g] = 0; S.is_proper[g] = 0; S.bwa_pick[g] = 0; S.active_molecule[g] = 0; S.duplicate[g] = 0; S.molecule_id[g] = -1; S.mapq[g] = 0;
@@ -349,7 +350,6 @@ __global__ void __launch_bounds__(256) k_rfa_init(int n_reads, DCand R, DInf S, 
     for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (i64)gridDim.x * blockDim.x) {
         S.active_idx[r] = -1; S.second_best_idx[r] = -1; S.split_idx[r] = -1; S.second_best_score[r] = 0; S.as_score[r] = 0;
         S.split_second_best[r] = 0; S.split_score[r] = 0; S.split_mapq[r] = 0;
-        for (i64 g = R.cand_off[r]; g < R.cand_off[r + 1] && g < cand_cap; ++g) S.cand_read[g] = (int32_t)r;
     }
 }
 // tagBestAlignments, one thread per pair (lariat.go:1474-1543).  Read 2 of a pair is always "touched" by read 1 (every read has >= 1 filtered candidate), so
@@ -362,6 +362,11 @@ __global__ void __launch_bounds__(256) k_rfa_tag(DOpts o, int n_pairs, const u64
     const int p = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
     int hv = 0;
     if (p < n_pairs && R.cand_off[2 * p + 2] <= cand_cap) {
+        // a read without a region: k_aln_prep marked its placeholder's slot -1 for k_aln_flat to pass over; the barcode program wants the read there
+        for (int h = 0; h < 2; ++h) {
+            const i64 c0 = R.cand_off[2 * p + h];
+            if (R.cand_off[2 * p + h + 1] - c0 == 1 && S.cand_read[c0] < 0) S.cand_read[c0] = 2 * p + h;
+        }
         int nA = 0, nM = 0;
         for (i64 a = R.cand_off[2 * p]; a < R.cand_off[2 * p + 1]; ++a) nA += R.in_filtered[a] != 0;
         for (i64 m = R.cand_off[2 * p + 1]; m < R.cand_off[2 * p + 2]; ++m) nM += R.in_filtered[m] != 0;
@@ -523,9 +528,10 @@ __global__ void __launch_bounds__(256) k_rfa_order(int n_bc, const int32_t* __re
         int acc = 0, nb = 0;
         for (int c = 0; c < 256; ++c) { start[c] = acc; acc += cnt[c]; if (c == 127) nb = acc; }
         counts[0] = n_bc; counts[1] = nb; counts[2] = n_bc - nb;
+        cnt[0] = nb;   // (the counts are consumed: the word carries n_big past the barrier — start[128] is being incremented by the time a late wave would read it)
     }
     __syncthreads();
-    const int n_big = start[128];
+    const int n_big = cnt[0];
     for (int bc = t; bc < n_bc; bc += 256) {
         const int c = cls_of(bc), at = atomicAdd(&start[c], 1);
         all[at] = bc;

@@ -119,6 +119,8 @@ struct lh_context {
     // K5, K6 (k_dedup.h, k_rescue2.h)
     int32_t* d_best = nullptr;
     uint8_t* d_reg_clean = nullptr;   // K5's word per read: its list needs no look before K6's replay (k_dedup.h)
+    uint8_t* d_dd_done = nullptr;     // K5's lane form ran where the read's extension finished (ExtArgs::dd_done): k_dedup_fast passes over the read
+    int32_t* d_dd_list = nullptr;     // the reads K5's lane form leaves to k_dedup (the count: d_ext_jobs->dd_need).  Its own: d_aln_r is being read by K4's long queue while the rounds append here
     int32_t* d_rnj = nullptr; i64* d_rjob_off = nullptr; RMeta* d_rmeta = nullptr; int32_t* d_rkeys = nullptr; int32_t* d_rheavy = nullptr;
     RJob* d_rjobs = nullptr; int32_t *d_rorder = nullptr, *d_rorder2 = nullptr; i64 rjob_cap = 0;   // K6's jobs (k_rescue2.h): they follow the batch
     // K7 (k_aln.h) and the result's candidate arrays
@@ -134,6 +136,7 @@ struct lh_context {
     uint8_t* d_slab_mid[2] = {nullptr, nullptr}; i64 slab_mid_bytes[2] = {0, 0}; int grid_rfa_mid[2] = {0, 0}; int grid_rfa_mid_max[2] = {0, 0};   // (r05) two tiers between the regular slabs and the few large ones
     int32_t* d_rfa_ovf_mid = nullptr;   // the tiers' overflow lists (RfaOvfMid)
     int32_t* d_rfa_order = nullptr;     // k_rfa_order's lists (RfaOrder)
+    bool rfa_pre = false;               // K8's prologue (rfa_prologue) was forked onto aux[0] beside K7: rfa_run joins it
     int32_t *d_rfa_ovf = nullptr, *d_rfa_ovf2 = nullptr, *d_rfa_hp = nullptr, *d_rfa_hr = nullptr; double* d_bc_lmp = nullptr;
     // timings
     hipEvent_t ev[LH_NSTAGE + 1];
@@ -219,6 +222,7 @@ static DOpts to_dopts(const lh_opts* o) {
 #define LH_POOL_FLOOR (1 << 16)   // the seed pools and the candidate pools start with room for this many entries at least
 #endif
 static int rfa_alloc(lh_context* c);
+static void rfa_prologue(lh_context* c, hipStream_t st);
 static int rfa_run(lh_context* c, const DOpts& o, int& t);
 static int stage2_alloc(lh_context* c);
 static int stage2_run(lh_context* c, const DOpts& o, int& t);
@@ -457,12 +461,15 @@ static int run_scan(lh_context* c, int n, const int32_t* in, int add, int at_lea
     return LH_OK;
 }
 
+static inline bool dedup_fused(const lh_context* c) { return !(c->flags & (LH_F_TAIL_PASSES | LH_F_EXT_WAVE)); }
 static ExtArgs ext_args(lh_context* c) {
     ExtArgs A;
     A.seq = c->b.seq; A.q4 = c->q4; A.seq_off = c->b.seq_off; A.seed_off = c->d_seed_off; A.chains = c->d_chains; A.cseeds = c->d_cseeds; A.n_chains = c->d_n_chains;
     A.sorder = c->d_srt; A.sdone = c->d_ord; A.chain_rmax = c->d_chain_rmax; A.reg_off = c->d_reg_off; A.regs = c->d_regs; A.n_regs = c->d_n_regs; A.est = c->d_ext_st;
     const ExtUnits U(c->d_ext_u, (size_t)c->pool_cap);
     A.nreg_u = U.nreg_u; A.u_read = U.u_read; A.est_u = U.est_u; A.rflag = ExtLongLists(c->d_ext_long, (size_t)c->cap_reads).rflag;
+    // K5 on the lane that finishes a read (not when K5 runs as a pass of its own, nor when no lane extends: LH_F_EXT_WAVE)
+    A.dd_best = c->d_best; A.dd_clean = c->d_reg_clean; A.dd_done = dedup_fused(c) ? c->d_dd_done : nullptr; A.dd_list = c->d_dd_list; A.dd_count = &c->d_ext_jobs->dd_need;
     return A;
 }
 
@@ -733,7 +740,7 @@ static BatchView part_view(const BatchView& whole, const RoundBufs& rb, const Ro
     return v;
 }
 
-// an error return may come between a fork onto an auxiliary stream (K3's cluster kernels, K4's wave kernels beside the rounds, K6's long-list replay, K8's routed
+// an error return may come between a fork onto an auxiliary stream (K3's cluster kernels, K4's wave kernels beside the rounds, K6's long-list replay, K8's prologue beside K7 and its routed
 // barcodes) and its join: nothing of the call may still be running on the context's buffers when the caller frees or reuses them
 static void quiesce(lh_context* c) {
     for (int i = 0; i < 3; ++i) hipStreamSynchronize(c->aux[i]);
@@ -858,7 +865,7 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
     if (!c->resident) return set_err(LH_E_ARG, "no batch resident: call lh_batch_upload first");
     if (opts->abi_version != LH_ABI_VERSION) return set_err(LH_E_ARG, "lh_opts.abi_version does not match LH_ABI_VERSION (use lh_opts_init)");
-    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
+    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
     HIPCHK(hipSetDevice(c->idx->device));
     {
         std::vector<void*> fl;

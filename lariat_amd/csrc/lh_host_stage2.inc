@@ -7,7 +7,7 @@ static int stage2_alloc(lh_context* c) {
     DevGroup& g = c->mem;
     DALLOC(g, c->d_reg_off, N + 1);
     DALLOC(g, c->d_n_regs, N); DALLOC(g, c->d_best, N);
-    DALLOC(g, c->d_reg_clean, N + 1); DALLOC(g, c->d_rnj, N / 2 + 1); DALLOC(g, c->d_rjob_off, N / 2 + 2); DALLOC(g, c->d_rmeta, 1); DALLOC(g, c->d_rheavy, N / 2 + 1); DALLOC(g, c->d_rkeys, 3 * LH_RC_KEYS);
+    DALLOC(g, c->d_reg_clean, N + 1); DALLOC(g, c->d_dd_done, N + 1); DALLOC(g, c->d_dd_list, N + 1); DALLOC(g, c->d_rnj, N / 2 + 1); DALLOC(g, c->d_rjob_off, N / 2 + 2); DALLOC(g, c->d_rmeta, 1); DALLOC(g, c->d_rheavy, N / 2 + 1); DALLOC(g, c->d_rkeys, 3 * LH_RC_KEYS);
     c->grid_aln = c->co.aln_grid;   // 92 VGPRs: 5 waves per SIMD
     DALLOC(g, c->d_zpool, (size_t)c->grid_aln * LH_ZSLAB);
     DALLOC(g, c->d_aln_count, 1);
@@ -312,10 +312,13 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
         }
     }
     T_BEGIN("k_dedup");
-    HIPCHK(hipMemsetAsync(&c->d_aln_count->flat, 0, sizeof(int32_t), c->stream));   // the list buffers are shared with K6 and K7, which run later
-    LH_LAUNCH(k_dedup_fast, (N + 255) / 256, 256, c->stream, ix, o, N, (const i64*)c->d_reg_off, c->d_regs, c->d_n_regs, c->d_best, c->d_aln_r, &c->d_aln_count->flat, c->d_reg_clean);
+    // the lane form for the reads that did not get it where their extension finished (every read: LH_F_TAIL_PASSES, LH_F_EXT_WAVE), then the wave kernel over what
+    // either listed.  The list's counter was cleared with K4's job block before K3 (run_front) and has been appended to since round 0
+    int32_t* const dd_count = &c->d_ext_jobs->dd_need;
+    LH_LAUNCH(k_dedup_fast, (N + 255) / 256, 256, c->stream, ix, o, N, (const i64*)c->d_reg_off, c->d_regs, c->d_n_regs, c->d_best, c->d_dd_list, dd_count, c->d_reg_clean,
+              (const uint8_t*)(dedup_fused(c) ? c->d_dd_done : nullptr));
     LH_LAUNCH(k_dedup, N < 16384 ? N : 16384, 64, c->stream, ix, o, N, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_regs_tmp, c->d_ia, c->d_n_regs, c->d_best, c->d_ctr,
-              (const int32_t*)c->d_aln_r, (const int32_t*)&c->d_aln_count->flat, c->d_reg_clean);
+              (const int32_t*)c->d_dd_list, (const int32_t*)dd_count, c->d_reg_clean);
     T_END();
     if (c->dump_stop_after_dedup) return LH_OK;
     T_BEGIN("k_rescue");
@@ -346,6 +349,11 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
             LH_LAUNCH(k_aln_flat, (int)((n_cand + 255) / 256), 256, c->stream, ix, o, n_cand, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->R, c->d_status, c->d_aln_r, c->d_aln_ci,
                       &c->d_aln_count->flat, c->d_ctr, c->q4, (const int32_t*)c->d_best, (const int32_t*)c->S.cand_read);
     }
+    // K8's prologue needs the candidate offsets and nothing else: the defaults of the inference columns and the barcodes' order run on the auxiliary stream beside
+    // K7's DP kernels, which touch none of what they write (rfa_run joins them before k_rfa_tag).  They start behind k_aln_flat — two passes over memory side by
+    // side only share its bandwidth — and are launched when K7's own launches are out, so that the device never waits for the host to issue them
+    c->rfa_pre = o.run_inference != 0 && !(c->flags & LH_F_TAIL_PASSES);
+    if (c->rfa_pre) HIPCHK(hipEventRecord(c->ev_fork, c->stream));
     const int g7 = N < c->grid_aln ? N : c->grid_aln;
     T_END();
     T_BEGIN("k_aln");
@@ -361,6 +369,11 @@ static int stage2_run(lh_context* c, const DOpts& o, int& t) {
               (const int32_t*)T7.wide_ci, (const int32_t*)&n7->grp32, c->d_aln_r, c->d_aln_ci, &n7->full);
     LH_LAUNCH(k_aln, g7, 64, c->stream, ix, o, N, c->b.seq, c->b.seq_off, c->d_reg_off, c->d_regs, c->d_n_regs, c->R, c->cand_cap, c->d_zpool, c->d_status, c->d_ctr,
               (const int32_t*)c->d_aln_r, (const int32_t*)c->d_aln_ci, (const int32_t*)&n7->full);
+    if (c->rfa_pre) {
+        HIPCHK(hipStreamWaitEvent(c->aux[0], c->ev_fork, 0));
+        rfa_prologue(c, c->aux[0]);
+        HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
+    }
     T_END();
     if (o.run_inference) { int rc = rfa_run(c, o, t); if (rc) return rc; }
     return LH_OK;
@@ -695,6 +708,13 @@ static int rfa_cascade(lh_context* c, const DOpts& o, bool post, RfaList in, i64
     return LH_OK;
 }
 
+// K8's prologue: the defaults of the inference columns and the order in which the barcode programs take their barcodes.  Both read the candidate offsets alone
+static void rfa_prologue(lh_context* c, hipStream_t st) {
+    const RfaOrder ord(c->d_rfa_order, (size_t)c->cap_bc);
+    LH_LAUNCH(k_rfa_init, 4096, 256, st, c->b.n_reads, c->R, c->S, c->cand_cap);
+    LH_LAUNCH(k_rfa_order, 1, 256, st, c->b.n_bc, (const int32_t*)c->b.bc_pair_off, c->R, ord.all, ord.big, ord.rest, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
+}
+
 static int rfa_run(lh_context* c, const DOpts& o, int& t) {
     RfaCounters* const ctr = c->d_bc_next;
     HIPCHK(hipMemsetAsync(ctr, 0, sizeof(RfaCounters), c->stream));
@@ -705,13 +725,13 @@ static int rfa_run(lh_context* c, const DOpts& o, int& t) {
     uint8_t* const wslab = small_ok ? c->d_slab : c->d_slab2;
     const i64 wslab_bytes = small_ok ? c->slab_bytes : c->slab2_bytes;
     const int wgrid = small_ok ? c->grid_rfa : c->grid_rfa2;
-    LH_LAUNCH(k_rfa_init, 4096, 256, c->stream, N, c->R, c->S, c->cand_cap);
+    if (c->rfa_pre) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[0], 0)); c->rfa_pre = false; }
+    else rfa_prologue(c, c->stream);
     LH_LAUNCH(k_rfa_tag, (P + 255) / 256, 256, c->stream, o, P, (const u64*)c->b.name_seed, c->R, c->S, c->cand_cap, c->d_rfa_hp, &ctr->heavy_pairs);
     LH_LAUNCH(k_rfa_tag_w, wgrid, 64, c->stream, o, (const u64*)c->b.name_seed, c->R, c->S, wslab, wslab_bytes, (const int32_t*)c->d_rfa_hp, (const int32_t*)&ctr->heavy_pairs, c->d_status);
     // (r06) most candidates first; the barcodes whose tables cannot fit a regular slab apart (k_rfa_order)
     const RfaOrder ord(c->d_rfa_order, (size_t)c->cap_bc);
     const RfaList all{ord.all, ord.n_all}, big{ord.big, ord.n_big}, rest{ord.rest, ord.n_rest};
-    LH_LAUNCH(k_rfa_order, 1, 256, c->stream, c->b.n_bc, (const int32_t*)c->b.bc_pair_off, c->R, ord.all, ord.big, ord.rest, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
     {
         // the first tier has slabs (an earlier batch needed them): the barcodes that cannot fit a regular slab start there at once, on a second stream, beside the first launch;
         // what they leave goes to the list the tier's own launch leaves its overflow in.  No slabs yet: the first launch sees every barcode and turns those away, as before

@@ -66,12 +66,12 @@ static_assert(offsetof(K1BigCounts, listed) == 0 && offsetof(K1BigCounts, asked)
 // the lengths of the candidate lists K7's kernels hand each other in lh_context::d_aln_r / d_aln_ci and the region scratch (RegsTmpLists).  The lists are shared
 // with K3, K5 and K6, which run earlier, and so are two of the counters: the ones a stage uses are cleared when it starts
 struct AlnCounts {
-    int32_t flat;    // candidates listed by k_aln_flat (k_aln_flat2's input).  Before K7: the reads k_dedup_fast lists for k_dedup; after it: the OR of the status words (k_status_or)
+    int32_t flat;    // candidates listed by k_aln_flat (k_aln_flat2's input).  After K7: the OR of the status words (k_status_or)
     int32_t grp16;   // what k_aln_flat2 lists for k_aln_grp<16>
     int32_t grp32;   // candidates listed for k_aln_grp<32>
     int32_t full;    // candidates listed for k_aln.  Before K7: the reads k_chain_cl leaves to k_chain
 };
-static_assert(offsetof(AlnCounts, flat) == 0 && sizeof(AlnCounts) == 4 * sizeof(int32_t), "K7 clears all four, K5 and the download the first");
+static_assert(offsetof(AlnCounts, flat) == 0 && sizeof(AlnCounts) == 4 * sizeof(int32_t), "K7 clears all four, the download the first");
 // K8's work counters and overflow counts: cleared as a whole when K8 starts
 struct RfaCounters {
     int32_t next;             // work counter of k_rfa's first launch
