@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LH_ABI_VERSION 8
+#define LH_ABI_VERSION 9
 
 /* status codes */
 #define LH_OK 0
@@ -82,6 +82,7 @@ typedef struct lh_opts {
 #define LH_F_RESCUE_FULL 256u     /* K6: every mate-rescue Smith-Waterman runs all rows of its window (default: the rows k_resc_cert proves sufficient, k_rescue3.h) */
 #define LH_F_SEED_LANE 512u       /* (ABI 7) K2: one lane per seed after a pass that names every seed slot's read (k_seed_owner + k_seed) and k_smem_fin sorting every read's intervals in memory before it; default: a 16-lane group per read that ranks its intervals itself, k_seed_grp */
 #define LH_F_TAIL_PASSES 1024u    /* (ABI 8) K5's lane form as a pass over every read after K4 (k_dedup_fast) and K8's prologue (k_rfa_init, k_rfa_order) after K7 on the main stream; default: a read's K5 on the lane that finishes its extension, the prologue beside K7 */
+#define LH_F_RFA_SLAB 2048u       /* (ABI 9) K8: every barcode through the regular instance of the barcode program, all its tables in the HBM slab (k_rfa<0>); default: the barcodes within LH_RFA_SM_* through the small instance, whose hot tables live in LDS (k_rfa<1>) */
 #define LH_F_CHAIN_WAVE 64u      /* K3: the reads a lane does not chain all go to the wave-per-seed kernel (k_chain), none to the cluster kernel (k_chain_cl) */
 
 /* how an index is made resident (lh_index_load / lh_index_from_arrays / lh_index_build_device); NULL = defaults */
@@ -344,6 +345,11 @@ typedef struct lh_round_info {
     int64_t max_barcode_need_bytes;  /* above the budget: LH_E_CAPACITY, the one barcode cannot be split */
 } lh_round_info;
 int lh_last_rounds(lh_context* ctx, int32_t lane, lh_round_info* out);
+
+/* (ABI 9) how K8 classed the barcodes of the last lh_align_resident: out[0 .. 3] = barcodes whose tables cannot fit a regular slab, the others beyond the small
+ * instance's caps, those listed for the small instance (0 under LH_F_RFA_SLAB, and for a batch with more than an eighth of its barcodes beyond the caps), and of the
+ * latter those the small instance turned away to the regular one (more molecules than its on-chip tables hold).  A test and measurement aid */
+int lh_last_rfa_classes(lh_context* ctx, int64_t* out /* [4] */);
 
 /* per-kernel timing of the last lh_align_resident (HIP events on the context's stream), ms; names are static strings.  After a run in rounds: per-kernel sums over the
  * rounds, plus "k1_discarded" (the K1 pass over the whole batch that found the overflow), "k_round_plan" and "k_batch_view" */

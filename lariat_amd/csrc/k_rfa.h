@@ -195,6 +195,32 @@ struct RfaTab {   // carved from the wave's slab
     int32_t* bestT;      // [R*M] best_alignment_for_read of molecule m for local read r at [r*M + m]; bit 30: it pairs with
                          // the molecule's best alignment of the mate read (static after markBest); -1: nil
 };
+// The tables the optimizer, the probability sums and the molecule status walk entry by entry, apart from the others: the regular instance of the barcode program
+// (k_rfa<0>) keeps them in the slab as 32-bit words (H.x = T.x), the small-barcode instance (k_rfa<1>) in LDS as 16-bit words for the whole barcode.  One address space
+// per instance, chosen at compile time: never a pointer that is LDS for one barcode and memory for another.
+template <typename I> struct RfaHot {
+    I *nbest, *aoff, *alen, *mflag;             // [M]
+    I *act_store;                                // [NCf]
+    I *act_cand, *act_slot, *tdel, *tset;        // [R]
+    double* P;                                   // [M]
+};
+// a barcode is `small` (k_rfa_order) when its candidates, its reads and the index's contigs are within these; its molecules are counted by the program itself, and one
+// with more than LH_RFA_SM_M of them leaves the small instance for the regular one.  256 reads = 128 pairs: the common 100-pair barcode with margin; 512 candidates: 2.5 a
+// read, twice what reads on unique sequence have; 128 molecules: one per pair (a library's barcodes hold one per three to ten pairs).  Test builds: a few each (-D).
+#ifndef LH_RFA_SM_NR
+#define LH_RFA_SM_NR 256
+#endif
+#ifndef LH_RFA_SM_NC
+#define LH_RFA_SM_NC 512
+#endif
+#ifndef LH_RFA_SM_M
+#define LH_RFA_SM_M 128
+#endif
+static_assert(LH_RFA_SM_NR < 32768 && LH_RFA_SM_NC < 32768 && LH_RFA_SM_M < 32768 && LH_RFA_SM_NR % 4 == 0 && LH_RFA_SM_NC % 4 == 0 && LH_RFA_SM_M % 4 == 0, "the small instance's tables are signed 16-bit words, each array 8-byte aligned");
+template <int SMALL> struct RfaHotWord { typedef int32_t type; };
+template <> struct RfaHotWord<1> { typedef int16_t type; };
+#define RFA_HOT_OFF (16 * LH_RFA_SRC_CHUNK)   // behind fastScore's staging (sLr, sFl, sLap)
+#define RFA_HOT_BYTES (8 * LH_RFA_SM_M + 2 * (4 * LH_RFA_SM_M + LH_RFA_SM_NC + 4 * LH_RFA_SM_NR))
 #define RFA_T_MASK 0x3fffffff
 #define RFA_T_PAIR 0x40000000
 
@@ -215,6 +241,8 @@ __device__ __forceinline__ int dev_mol_active(int alen, int nbest, int change) {
 static_assert(LH_RFA_LDS_BYTES >= LH_MAPQ_TOP * 64 * (int)sizeof(double), "estimateMapQualities keeps a read's top-15 scores per lane in lds_raw (top[k * 64 + lane])");
 #define LH_RFA_NCONT_LDS 1024  // contig slots of a barcode kept in LDS while grouping (index with more contigs: slab copy)
 #define LH_RFA_SRC_CHUNK 256   // source-molecule alignments staged per pass of fastScore
+static_assert(RFA_HOT_OFF + RFA_HOT_BYTES <= LH_RFA_LDS_BYTES && LH_RFA_SM_NR <= LH_RFA_SRC_CHUNK && LH_RFA_SM_NC <= LH_RFA_SORT_LDS,
+              "the small instance: hot tables behind the staging of a whole source (at most a barcode's reads), every contig list sorted in LDS");
 #ifndef LH_RFA_MOL_LDS_MIN
 #ifndef LH_RFA_TIE_LDS
 #define LH_RFA_TIE_LDS (LH_RFA_LDS_BYTES / 4 < 4096 ? LH_RFA_LDS_BYTES / 4 : 4096)   // entries of a contig list with two equal positions that Go's algorithm sorts as 32-bit words in LDS (test builds: 100)
@@ -234,21 +262,22 @@ static_assert(LH_RFA_NET_BLOCK >= 64 && (LH_RFA_NET_BLOCK & (LH_RFA_NET_BLOCK - 
 // reads that would move (toDelete / toSet) to T.tdel / T.tset and their number to *nmove.
 // (r06, late) `staged`: the source's alignments are in LDS already — the caller has scored another 64 sinks of the SAME source since nothing changed (a source of up to
 // LH_RFA_SRC_CHUNK alignments: longer ones are staged chunk by chunk on every call).  Staging was repeated per 64 sinks: half of a call on a barcode of hundreds of molecules.
-__device__ __forceinline__ double dev_fast_score_w(const DCand& R, const DInf& S, const RfaTab& T, i64 c_lo, int r0, int M, int src, int snk, double lup,
+template <typename HOT>
+__device__ __forceinline__ double dev_fast_score_w(const DCand& R, const DInf& S, const RfaTab& T, const HOT& H, i64 c_lo, int r0, int M, int src, int snk, double lup,
                                                    int32_t* sLr, int32_t* sFl, double* sLap, int* num_out, int record, int* nmove, int staged = 0) {
     const int lane = LANE();
     double change = 0, alignment_change = 0;
     int num = 0, nm = 0;
-    const int n = T.alen[src], ao = T.aoff[src];
+    const int n = H.alen[src], ao = H.aoff[src];
     const int reuse = staged && n <= LH_RFA_SRC_CHUNK;
     for (int cb = 0; cb < n; cb += LH_RFA_SRC_CHUNK) {
         int cn = n - cb < LH_RFA_SRC_CHUNK ? n - cb : LH_RFA_SRC_CHUNK;
         if (!reuse) {
             EMU_SYNC();   // the previous chunk has been consumed
             for (int s = lane; s < cn; s += 64) {
-                int a = T.act_store[ao + cb + s];
+                int a = H.act_store[ao + cb + s];
                 int lr = S.cand_read[c_lo + a] - r0;
-                int sm = T.act_cand[lr ^ 1];
+                int sm = H.act_cand[lr ^ 1];
                 int hm = sm >= 0 && S.molecule_id[c_lo + sm] == src;          // source_has_mate
                 int hp = hm && dev_is_pair(R, c_lo + a, c_lo + sm);           // source_has_mate_pair
                 sLr[s] = lr; sFl[s] = hm | hp << 1; sLap[s] = R.lap[c_lo + a];
@@ -273,7 +302,7 @@ __device__ __forceinline__ double dev_fast_score_w(const DCand& R, const DInf& S
                         int hm = fl & 1, hp = fl >> 1;
                         int skp = (tq & RFA_T_PAIR) && hm;                    // sink_has_mate_pair
                         if (!hp || (hm && skp)) {
-                            if (record) { T.tdel[nm] = sLr[s]; T.tset[nm] = t; }
+                            if (record) { H.tdel[nm] = sLr[s]; H.tset[nm] = t; }
                             nm++;
                         }
                         alignment_change += lap4[u] - sLap[s];
@@ -286,12 +315,12 @@ __device__ __forceinline__ double dev_fast_score_w(const DCand& R, const DInf& S
         }
     }
     if (snk >= 0) {
-        int sb = dev_mol_active(T.alen[src], T.nbest[src], 0), sa = dev_mol_active(T.alen[src], T.nbest[src], -num);
-        if (!sa && sb) change -= (double)T.nbest[src] * -0.5;
-        int kb = dev_mol_active(T.alen[snk], T.nbest[snk], 0), ka = dev_mol_active(T.alen[snk], T.nbest[snk], num);
-        if (ka && !kb) change += (double)T.nbest[snk] * -0.5;
-        if (T.alen[src] - num == 0 && num > 0) change -= -3.0;
-        if (T.alen[snk] == 0 && num > 0) change += -3.0;
+        int sb = dev_mol_active(H.alen[src], H.nbest[src], 0), sa = dev_mol_active(H.alen[src], H.nbest[src], -num);
+        if (!sa && sb) change -= (double)H.nbest[src] * -0.5;
+        int kb = dev_mol_active(H.alen[snk], H.nbest[snk], 0), ka = dev_mol_active(H.alen[snk], H.nbest[snk], num);
+        if (ka && !kb) change += (double)H.nbest[snk] * -0.5;
+        if (H.alen[src] - num == 0 && num > 0) change -= -3.0;
+        if (H.alen[snk] == 0 && num > 0) change += -3.0;
         change += alignment_change;
     }
     *num_out = num;
@@ -495,18 +524,29 @@ __device__ __forceinline__ size_t rfa_carve_bytes(int NC, int nR, int ncmax) {
     return (so + 7) & ~(size_t)7;
 }
 
+constexpr int rfa_hbits_c(int nR) { int h = 6; while ((1 << h) < 2 * nR) ++h; return h; }
+// what the small instance asks of a slab: its carve at the caps and the molecule x read table at the caps
+__device__ __forceinline__ size_t rfa_small_bytes() { return rfa_carve_bytes(LH_RFA_SM_NC, LH_RFA_SM_NR, LH_RFA_NCONT_LDS) + (size_t)4 * LH_RFA_SM_M * LH_RFA_SM_NR; }
+
 // (r06) the order in which the barcode programs take their barcodes: most candidates first.  A barcode's time grows faster than its candidate count (the position sorts,
 // the molecule x read tables), a wave takes one barcode at a time, and the launch lasts until its last barcode is done: in index order the largest barcode of a batch
 // could start last (kernel_ms_by_step of the repeats leg: 119 / 93 / 90 ms on three read sets).  A counting sort by size class (a quarter of an octave of the
 // candidate count), one block; order[n_bc] = n_bc, the list's length as k_rfa's work_count wants it.
 // all[0 .. n_bc): every barcode, largest first (k_rfa_post's list); big[]: those whose tables cannot fit a regular slab (slab_bytes), largest first — they go straight to the
 // first tier's slabs, beside the others, instead of being turned away by the first launch and started when it has ended (a batch with log-normal barcode sizes: 61 ms, then 77 ms
-// for the turned-away ones) —; rest[]: the others.  counts = {n_bc, n_big, n_bc - n_big}.
+// for the turned-away ones) —; small[]: those the small instance of the barcode program takes (r13, below); rest[]: the others.  counts = {n_bc, n_big, n_rest, n_small}.
 __global__ void __launch_bounds__(256) k_rfa_order(int n_bc, const int32_t* __restrict__ bc_pair_off, DCand R, int32_t* __restrict__ all, int32_t* __restrict__ big, int32_t* __restrict__ rest,
-                                                    int32_t* __restrict__ counts, i64 slab_bytes, int ncmax) {
-    __shared__ int32_t cnt[256], start[256];
+                                                    int32_t* __restrict__ small, int merge_big, int32_t* __restrict__ counts, i64 slab_bytes, int ncmax) {
+    // (r13) a third class, small[]: the barcodes within the caps of the small instance of the barcode program (LH_RFA_SM_NC candidates, LH_RFA_SM_NR reads, a contig
+    // table that fits LDS), largest first, behind the others in all[]; small == null (LH_F_RFA_SLAB): none.  The small instance has a launch of its own in front of the regular
+    // one's, and two launches in a row each end with a barcode's time at falling occupancy: that pays where nearly every barcode is small, so the block lists small barcodes only
+    // where at most an eighth of the batch is beyond the caps — otherwise they are `rest` and the batch runs as one launch of the regular instance (reads on repeat families: most
+    // barcodes beyond the caps).  merge_big (the host has no first-tier slabs to route the big ones to): rest[] = the big ones, then the others — all[]'s order —, one list
+    // for one launch of the regular instance, which turns the big ones away.  counts = {n_bc, n_big, length of rest[], n_small, unused, length of rest[] as written here}:
+    // counts[2] grows while the small instance runs (the barcodes it turns away), counts[5] does not.
+    __shared__ int32_t cnt[384], start[384], sh_split;
     const int t = threadIdx.x;
-    cnt[t] = 0;
+    for (int c = t; c < 384; c += 256) cnt[c] = 0;
     __syncthreads();
     auto cls_of = [&](int bc) {
         const int p0 = bc_pair_off[bc], p1 = bc_pair_off[bc + 1];
@@ -520,24 +560,37 @@ __global__ void __launch_bounds__(256) k_rfa_order(int n_bc, const int32_t* __re
         // away late starts again when the first launch has ended
         const size_t nr_ = (size_t)(2 * (p1 - p0));
         const int is_big = nc < 0x7fffffff && rfa_carve_bytes((int)nc, 2 * (p1 - p0), ncmax) + nr_ * nr_ > (size_t)slab_bytes;
-        return (is_big ? 0 : 128) + 127 - (c < 127 ? c : 127);           // the big ones first, large classes first
+        const int is_small = small && !is_big && nc <= LH_RFA_SM_NC && nr_ <= (size_t)LH_RFA_SM_NR && ncmax <= LH_RFA_NCONT_LDS && rfa_small_bytes() <= (size_t)slab_bytes;
+        return (is_big ? 0 : is_small ? 256 : 128) + 127 - (c < 127 ? c : 127);           // the big ones first, the small ones last, large classes first
     };
     for (int bc = t; bc < n_bc; bc += 256) atomicAdd(&cnt[cls_of(bc)], 1);
     __syncthreads();
     if (t == 0) {
-        int acc = 0, nb = 0;
-        for (int c = 0; c < 256; ++c) { start[c] = acc; acc += cnt[c]; if (c == 127) nb = acc; }
-        counts[0] = n_bc; counts[1] = nb; counts[2] = n_bc - nb;
-        cnt[0] = nb;   // (the counts are consumed: the word carries n_big past the barrier — start[128] is being incremented by the time a late wave would read it)
+        int beyond = 0;
+        for (int c = 0; c < 256; ++c) beyond += cnt[c];
+        const int split = 8 * (i64)beyond <= (i64)n_bc;
+        sh_split = split;
+        if (!split) for (int c = 256; c < 384; ++c) { cnt[c - 128] += cnt[c]; cnt[c] = 0; }
+        int acc = 0, nb = 0, nr = 0;
+        for (int c = 0; c < 384; ++c) { start[c] = acc; acc += cnt[c]; if (c == 127) nb = acc; if (c == 255) nr = acc - nb; }
+        counts[0] = n_bc; counts[1] = nb; counts[2] = merge_big ? nb + nr : nr; counts[3] = n_bc - nb - nr; counts[4] = 0; counts[5] = counts[2];
+        cnt[0] = nb; cnt[1] = nr;   // (the counts are consumed: the words carry n_big and n_rest past the barrier — start[] is being incremented by the time a late wave would read it)
     }
     __syncthreads();
-    const int n_big = cnt[0];
+    const int n_big = cnt[0], n_rest = cnt[1], split = sh_split;
     for (int bc = t; bc < n_bc; bc += 256) {
-        const int c = cls_of(bc), at = atomicAdd(&start[c], 1);
+        int c = cls_of(bc);
+        if (c >= 256 && !split) c -= 128;
+        const int at = atomicAdd(&start[c], 1);
         all[at] = bc;
-        if (c < 128) big[at] = bc; else rest[at - n_big] = bc;
+        if (c < 128) { big[at] = bc; if (merge_big) rest[at] = bc; }
+        else if (c < 256) rest[merge_big ? at : at - n_big] = bc;
+        else small[at - n_big - n_rest] = bc;
     }
 }
+
+// the classes of the batch for lh_last_rfa_classes, one word: the barcodes listed as small, and above them those the small instance turned away
+__global__ void k_peek_rfa(const int32_t* __restrict__ counts, i64* __restrict__ dst_host) { dst_host[0] = (i64)counts[3] | (i64)(counts[2] - counts[5]) << 32; }
 
 // development aid (tools/prof_rfa.sh builds a library with -DLH_RFA_PROF): shader-clock time per phase of the barcode program, summed over the waves
 #ifdef LH_RFA_PROF
@@ -545,6 +598,12 @@ __device__ unsigned long long lh_rfa_prof[24];
 #define RFA_PROF(k_) { const unsigned long long now_ = (unsigned long long)clock64(); if (lane == 0) atomicAdd(&lh_rfa_prof[k_], now_ - prof_t_); prof_t_ = (unsigned long long)clock64(); }
 #else
 #define RFA_PROF(k_)
+#endif
+// (the small instance) `lane` re-read as a value the compiler cannot look through, at a phase's end: the lane's table addresses of one phase are not kept for the next
+#ifdef LH_EMU
+#define RFA_FENCE()
+#else
+#define RFA_FENCE() { if constexpr (SMALL) asm volatile("" : "+v"(lane)); }
 #endif
 #ifndef LH_RFA_WAVES
 #ifdef LH_RA_HIST
@@ -554,6 +613,11 @@ __device__ int lh_rfa_bcstat[4096][8];   // per barcode (index mod 4096): 10 ns 
 #endif
 #define LH_RFA_WAVES 4   // waves per SIMD the register budget is sized for (128 VGPRs + 64 spilled: the kernel waits on memory, 4 waves hide more of it than 2 waves of 190 registers)
 #endif
+// (r13) SMALL = 1: the instance for the barcodes k_rfa_order lists as small (LH_RFA_SM_*).  Its hot tables (RfaHot) live in LDS from scrapMolecules to the molecule
+// penalty, behind fastScore's staging; the branches only larger barcodes take (grouping through LDS atomics, contig lists longer than the sort buffer, the contig
+// tables in the slab) are not compiled into it.  A barcode beyond the caps, or with more than LH_RFA_SM_M molecules once they are counted, is appended to ovf_list —
+// the regular instance's work list, whose launch follows on the same stream — before anything of it has been written that the regular instance does not write again.
+template <int SMALL>
 __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, int n_bc, const int32_t* __restrict__ bc_pair_off, const uint8_t* __restrict__ bc_do_rfa,
                                              const u64* __restrict__ name_seed, const i64* __restrict__ cen_start, const i64* __restrict__ cen_end, DCand R, DInf S, i64 cand_cap,
                                              uint8_t* __restrict__ slab_pool, i64 slab_bytes, int32_t* __restrict__ status, int32_t* __restrict__ bc_next,
@@ -561,14 +625,18 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                                              int32_t* __restrict__ ovf_count, int32_t* __restrict__ hr_list, int32_t* __restrict__ hr_count, double* __restrict__ bc_lmp) {
     __shared__ int32_t shi[8];
     __shared__ double shd[4];
-    __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LH_RFA_LDS_BYTES];   // one buffer, re-used phase by phase
+    // one buffer, re-used phase by phase: contig tables (grouping) | keys and places (position sort) | a tile's records and read numbers (markBest, step 1) |
+    // fastScore's source staging (optimizer, probability sums) | the lanes' top-15 scores (estimateMapQualities).  The small instance keeps its hot tables behind the
+    // staging, [RFA_HOT_OFF, RFA_HOT_OFF + RFA_HOT_BYTES): written from scrapMolecules on — markBest's tiles are done by then —, last read by the molecule penalty —
+    // the top-15 scores come after it.  Nothing else touches lds_raw in between.
+    __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LH_RFA_LDS_BYTES];
     i64* const spos = (i64*)lds_raw;                                               // position sort
     int32_t* const sidx = (int32_t*)(lds_raw + 8 * LH_RFA_SORT_LDS);
     int32_t* const sLr = (int32_t*)lds_raw;                                        // fastScore source staging
     int32_t* const sFl = sLr + LH_RFA_SRC_CHUNK;
     double* const sLap = (double*)(sFl + LH_RFA_SRC_CHUNK);
-    const int lane = LANE();
-    uint8_t* slab = slab_pool + (size_t)blockIdx.x * (size_t)slab_bytes;
+    const int lane_k = LANE();
+    uint8_t* const slab_k = slab_pool + (size_t)blockIdx.x * (size_t)slab_bytes;
     const double improper = o.improper_pair_penalty;
     const int n_work = work_list ? *work_count : n_bc;
 #define RFA_OVERFLOW()                                                                                 \
@@ -581,6 +649,16 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
     }
     int wd_main = 1 << 24;
     for (;;) {
+        // (the small instance's table addresses are the same for every barcode — a slab's base, a lane, constants —, and the compiler kept them all in registers
+        // across the whole kernel: sixty spilled words.  Base and lane are re-read here as values it cannot look through, so an address lives where it is used.)
+        int lane = lane_k;
+        uint8_t* slab = slab_k;
+#if !defined(LH_EMU)
+        if constexpr (SMALL) {
+            asm volatile("" : "+s"(slab));
+            asm volatile("" : "+v"(lane));
+        }
+#endif
         LH_WATCH(o.wd, wd_main, 12, break)
         if (lane == 0) shi[5] = atomicAdd(bc_next, 1);
         WAVE_SYNC();
@@ -605,19 +683,40 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         RfaTab T;
 #define CARVE(ptr, type, count) { so = (so + 7) & ~(size_t)7; T.ptr = (type*)(slab + so); so += sizeof(type) * (size_t)(count); }
         int ncmax = ix.n_contigs + 2;
-        int hbits = 6;
-        while ((1 << hbits) < 2 * nR) ++hbits;
-        LH_RFA_CARVE_LIST(CARVE)
+        if constexpr (SMALL) {
+            // the small instance carves for its caps, not for the barcode: every table at a fixed place of the slab — one base and constants, where forty table
+            // addresses held across the whole program spilled (k_rfa_order lists a barcode as small only where a slab holds this carve: rfa_small_bytes)
+            constexpr int NC = LH_RFA_SM_NC, nR = LH_RFA_SM_NR, ncmax = LH_RFA_NCONT_LDS, hbits = rfa_hbits_c(LH_RFA_SM_NR);
+            LH_RFA_CARVE_LIST(CARVE)
+        } else {
+            int hbits = 6;
+            while ((1 << hbits) < 2 * nR) ++hbits;
+            LH_RFA_CARVE_LIST(CARVE)
+        }
         so = (so + 7) & ~(size_t)7;
         T.bestT = (int32_t*)(slab + so);
         size_t best_cap = ((size_t)slab_bytes > so) ? ((size_t)slab_bytes - so) / 4 : 0;
 #undef CARVE
         if (so > (size_t)slab_bytes) RFA_OVERFLOW()   // barcode too large for the slab
+        typedef typename RfaHotWord<SMALL>::type hot_t;
+        RfaHot<hot_t> H;
+        if constexpr (SMALL) {
+            if (NC > LH_RFA_SM_NC || nR > LH_RFA_SM_NR || ncmax > LH_RFA_NCONT_LDS) RFA_OVERFLOW()   // (k_rfa_order lists none of these as small: the tables below are sized by the caps)
+            uint8_t* const hot = lds_raw + RFA_HOT_OFF;
+            H.P = (double*)hot;
+            hot_t* const hw = (hot_t*)(hot + 8 * LH_RFA_SM_M);
+            H.nbest = hw; H.aoff = hw + LH_RFA_SM_M; H.alen = hw + 2 * LH_RFA_SM_M; H.mflag = hw + 3 * LH_RFA_SM_M;
+            H.act_store = hw + 4 * LH_RFA_SM_M;
+            H.act_cand = H.act_store + LH_RFA_SM_NC; H.act_slot = H.act_cand + LH_RFA_SM_NR; H.tdel = H.act_slot + LH_RFA_SM_NR; H.tset = H.tdel + LH_RFA_SM_NR;
+        } else {
+            H.P = T.P; H.nbest = T.nbest; H.aoff = T.aoff; H.alen = T.alen; H.mflag = T.mflag; H.act_store = T.act_store;
+            H.act_cand = T.act_cand; H.act_slot = T.act_slot; H.tdel = T.tdel; H.tset = T.tset;
+        }
         // (measured, r05: guessing from NC and nR that the molecule x read table will not fit — to spare a barcode three phases in a tier it outgrows — sends on too many that do fit:
         // one candidate in four to sixteen starts a molecule, and a barcode sent on waits for one of fewer waves; 4,000 x 100 pairs 108 -> 155 ms, 1,000 x 400 pairs 0.44 -> 1.1 s)
         // ---- positions: filtered candidates grouped by contig in first-seen order, candidate order inside a contig ----
         int ncont = 0, NCf = 0;
-        if (ncmax <= LH_RFA_NCONT_LDS && NC > 256) {
+        if (!SMALL && ncmax <= LH_RFA_NCONT_LDS && NC > 256) {
             // (r06) a large barcode, a contig table that fits LDS: the contigs' first-seen order from one atomic minimum per candidate (the smallest candidate index
             // that names the contig), slot sizes from one atomic add, and the stable placement from the lanes that share a slot — found with one ballot per bit of
             // the slot number, not one loop turn per slot present in the chunk (a read on repeat families names thirty contigs: the three passes were a sixth of the
@@ -676,8 +775,8 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             }
         } else {
         // pass A: contig slot of every candidate (first-seen numbering) and the slot sizes
-        int32_t* const seen = ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw : T.seen_rid;
-        int32_t* const scnt = ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw + LH_RFA_NCONT_LDS : T.ccnt;
+        int32_t* const seen = SMALL || ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw : T.seen_rid;
+        int32_t* const scnt = SMALL || ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw + LH_RFA_NCONT_LDS : T.ccnt;
         for (int base = 0; base < NC; base += 64) {
             int a = base + lane;
             int valid = a < NC && R.in_filtered[c_lo + a];
@@ -734,6 +833,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         WAVE_SYNC();
         }
         RFA_PROF(3)
+        RFA_FENCE()
         // sort.Sort(ByPosition) per contig (lariat.go:1545-1547), one lane per contig; keys staged in LDS when they fit
         if (NCf <= LH_RFA_SORT_LDS && ncont <= 8) {
             // Few contigs: the wave sorts one contig at a time by ranking (every lane counts the smaller keys of its elements).
@@ -761,7 +861,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                     for (int e = lane; e < n; e += 64) T.plist[b0 + e] = ip[e];
                 }
             }
-        } else if (NCf <= LH_RFA_SORT_LDS) {
+        } else if (SMALL || NCf <= LH_RFA_SORT_LDS) {
             for (int i = lane; i < NCf; i += 64) { sidx[i] = T.plist[i]; spos[i] = R.pos[c_lo + T.plist[i]]; }
             WAVE_SYNC();
             for (int k = lane; k < ncont; k += 64) {
@@ -964,6 +1064,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         }
         WAVE_SYNC();
         RFA_PROF(4)
+        RFA_FENCE()
         int do_rfa = bc_do_rfa[bc] != 0;
         int M = 0;
         if (do_rfa) {
@@ -990,6 +1091,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             if (lane == 0) T.mstart[Mraw] = NCf;
             WAVE_SYNC();
             RFA_PROF(16)
+            RFA_FENCE()
 #ifdef LH_RA_HIST
             {
                 int mxs = 0;
@@ -1144,6 +1246,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             if (lane == 0) { T.psum[NCf] = nfirst; T.actc[NCf] = nactive; }
             WAVE_SYNC();
             RFA_PROF(5)
+            RFA_FENCE()
             // ---- scrapMolecules: keep molecules with an active alignment, renumber ----
             int ao = 0;
             for (int base = 0; base < Mraw; base += 64) {
@@ -1153,15 +1256,19 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 u64 mk = __ballot(keep);
                 int id = M + lanes_below(mk, lane);
                 int inc = wave_scan_add_i32(nr);
-                if (keep) { T.newid[m] = id; T.seg0[id] = T.mstart[m]; T.seg1[id] = T.mstart[m + 1]; T.nbest[id] = nr; T.aoff[id] = ao + inc - nr; T.alen[id] = 0; }
+                if (keep) {
+                    T.newid[m] = id; T.seg0[id] = T.mstart[m]; T.seg1[id] = T.mstart[m + 1];
+                    if (!SMALL || id < LH_RFA_SM_M) { H.nbest[id] = nr; H.aoff[id] = ao + inc - nr; H.alen[id] = 0; }   // (small: the on-chip tables end at LH_RFA_SM_M; more molecules: turned away below)
+                }
                 else if (m < Mraw) T.newid[m] = -1;
                 M += __popcll(mk);
                 ao += wave_readlane(inc, 63);
             }
             WAVE_SYNC();
+            if (SMALL && M > LH_RFA_SM_M) RFA_OVERFLOW()   // more molecules than the on-chip tables hold: the regular instance takes the barcode from the start
             if ((size_t)M * (size_t)nR > best_cap) RFA_OVERFLOW()   // molecule table does not fit the slab
             for (size_t x = lane; x < (size_t)M * nR; x += 64) T.bestT[x] = -1;
-            for (int r = lane; r < nR; r += 64) { T.act_cand[r] = -1; T.act_slot[r] = -1; T.dk0[r] = 0; }   // (dk0: k_rfa_post's; here the read's sink groups, below)
+            for (int r = lane; r < nR; r += 64) { H.act_cand[r] = -1; H.act_slot[r] = -1; T.dk0[r] = 0; }   // (dk0: k_rfa_post's; here the read's sink groups, below)
             for (int i = lane; i < NCf; i += 64) S.molecule_id[c_lo + T.plist[i]] = T.newid[T.molraw[i]];
             WAVE_SYNC();
             // step 2: per molecule, reads in first-occurrence order: best alignment (earliest maximum) and the active list
@@ -1218,31 +1325,32 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 int act = T.actc[i];
                 if (act >= 0) {
                     int slot = T.psum[i] - T.psum[T.seg0[m]];
-                    T.act_store[T.aoff[m] + slot] = act; T.act_cand[lr] = act; T.act_slot[lr] = slot;
+                    H.act_store[H.aoff[m] + slot] = act; H.act_cand[lr] = act; H.act_slot[lr] = slot;
                 }
             }
-            for (int m = lane; m < M; m += 64) T.alen[m] = T.psum[T.seg1[m]] - T.psum[T.seg0[m]];
+            for (int m = lane; m < M; m += 64) H.alen[m] = T.psum[T.seg1[m]] - T.psum[T.seg0[m]];
             WAVE_SYNC();
             // setMoleculeDifferences(candidate_molecules, false) before the optimizer (lariat.go:503): alignments that are
             // active NOW keep this value even if a later move deactivates them
             for (int m = lane; m < M; m += 64) {
                 int diffs = 0;
-                for (int k = 0; k < T.alen[m]; ++k) diffs += R.mismatches[c_lo + T.act_store[T.aoff[m] + k]];
-                double diff = (double)diffs / (double)T.alen[m];
-                for (int k = 0; k < T.alen[m]; ++k) S.mol_diff[c_lo + T.act_store[T.aoff[m] + k]] = diff;
+                for (int k = 0; k < H.alen[m]; ++k) diffs += R.mismatches[c_lo + H.act_store[H.aoff[m] + k]];
+                double diff = (double)diffs / (double)H.alen[m];
+                for (int k = 0; k < H.alen[m]; ++k) S.mol_diff[c_lo + H.act_store[H.aoff[m] + k]] = diff;
             }
             WAVE_SYNC();
             RFA_PROF(6)
+            RFA_FENCE()
             // ---- optimizer.Optimize(opt, 1, 2, 4*M): 8*M greedy molecule moves ----
             // The optimizer is deterministic: once M consecutive turns (every molecule tried once as the source) accept no
             // move, the state can no longer change and the remaining turns are no-ops, so they are not executed.
             // the source staged once (a call with idle lanes), and the groups of 64 sinks in which one of its reads has an alignment: the union of its reads' group bits
             auto stage_source = [&](int src) -> u64 {
-                if (M <= 64 || T.alen[src] > LH_RFA_SRC_CHUNK) return ~0ull;
+                if (M <= 64 || H.alen[src] > LH_RFA_SRC_CHUNK) return ~0ull;
                 int num;
-                dev_fast_score_w(R, S, T, c_lo, r0, M, src, -1, improper, sLr, sFl, sLap, &num, 0, (int*)0);
+                dev_fast_score_w(R, S, T, H, c_lo, r0, M, src, -1, improper, sLr, sFl, sLap, &num, 0, (int*)0);
                 u64 mine = 0;
-                for (int k = lane; k < T.alen[src]; k += 64) mine |= T.dk0[sLr[k]];
+                for (int k = lane; k < H.alen[src]; k += 64) mine |= T.dk0[sLr[k]];
                 u64 all = 0;
                 for (int b = 0; b < 64 && b * 64 < M; ++b)
                     if (__ballot((int)(mine >> b & 1))) all |= 1ull << b;
@@ -1252,7 +1360,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             int source = 0, idle = 0;
             for (int it = 0; it < 8 * M && idle < M; ++it) {
                 ++idle;
-                if (T.alen[source] == 0) { source = (source + 1) % M; continue; }
+                if (H.alen[source] == 0) { source = (source + 1) % M; continue; }
                 double bs = -1.7976931348623157e308;
                 int bl = -1, bi = 0x7fffffff;
                 const u64 groups = stage_source(source);
@@ -1261,8 +1369,8 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                     if (!(groups >> ((sb >> 6) & 63) & 1)) continue;   // (no sink here has a read of the source to move: num = 0 for all of them)
                     int i = sb + lane, num;
                     int snk = (i < M && i != source) ? i : -1;
-                    double sc = dev_fast_score_w(R, S, T, c_lo, r0, M, source, snk, improper, sLr, sFl, sLap, &num, 0, (int*)0, staged);
-                    if (snk >= 0 && num > 0 && (sc > bs || (sc == bs && T.alen[i] > bl))) { bs = sc; bl = T.alen[i]; bi = i; }
+                    double sc = dev_fast_score_w(R, S, T, H, c_lo, r0, M, source, snk, improper, sLr, sFl, sLap, &num, 0, (int*)0, staged);
+                    if (snk >= 0 && num > 0 && (sc > bs || (sc == bs && H.alen[i] > bl))) { bs = sc; bl = H.alen[i]; bi = i; }
                 }
                 for (int msk = 32; msk >= 1; msk >>= 1) {   // lexicographic max of (score, sink size), first index on full ties
                     double os = __shfl_xor(bs, msk);
@@ -1270,25 +1378,25 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                     int take = oi != 0x7fffffff && (bi == 0x7fffffff || os > bs || (os == bs && (ol > bl || (ol == bl && oi < bi))));
                     if (take) { bs = os; bl = ol; bi = oi; }
                 }
-                if (bi != 0x7fffffff && (bs > 0 || (bs == 0 && bl > T.alen[source]))) {
+                if (bi != 0x7fffffff && (bs > 0 || (bs == 0 && bl > H.alen[source]))) {
                     int num, nmv;   // acceptMove: recompute the move list (every lane evaluates the winner, lane 0 records), apply in order
-                    dev_fast_score_w(R, S, T, c_lo, r0, M, source, bi, improper, sLr, sFl, sLap, &num, lane == 0, &nmv, staged);
+                    dev_fast_score_w(R, S, T, H, c_lo, r0, M, source, bi, improper, sLr, sFl, sLap, &num, lane == 0, &nmv, staged);
                     WAVE_SYNC();
                     idle = 0;
                     if (lane == 0) {
                         for (int k = 0; k < nmv; ++k) {
-                            int lr = T.tdel[k], t = T.tset[k];
-                            int a = T.act_cand[lr], slot = T.act_slot[lr];
-                            int last = T.alen[source] - 1;
-                            if (T.alen[source] > 1) {
-                                int mv = T.act_store[T.aoff[source] + last];
-                                T.act_store[T.aoff[source] + slot] = mv;
-                                T.act_slot[S.cand_read[c_lo + mv] - r0] = slot;
+                            int lr = H.tdel[k], t = H.tset[k];
+                            int a = H.act_cand[lr], slot = H.act_slot[lr];
+                            int last = H.alen[source] - 1;
+                            if (H.alen[source] > 1) {
+                                int mv = H.act_store[H.aoff[source] + last];
+                                H.act_store[H.aoff[source] + slot] = mv;
+                                H.act_slot[S.cand_read[c_lo + mv] - r0] = slot;
                             }
-                            T.alen[source] = last;
-                            T.act_store[T.aoff[bi] + T.alen[bi]] = t;
-                            T.act_slot[lr] = T.alen[bi]; T.act_cand[lr] = t;
-                            T.alen[bi]++;
+                            H.alen[source] = last;
+                            H.act_store[H.aoff[bi] + H.alen[bi]] = t;
+                            H.act_slot[lr] = H.alen[bi]; H.act_cand[lr] = t;
+                            H.alen[bi]++;
                             S.active[c_lo + a] = 0; S.active[c_lo + t] = 1;
                         }
                     }
@@ -1297,6 +1405,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 source = (source + 1) % M;
             }
             RFA_PROF(7)
+            RFA_FENCE()
             // ---- moleculeMapqProbabilitySums ----
             for (int s = 0; s < M; ++s) {
                 const u64 groups = stage_source(s);
@@ -1304,13 +1413,13 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 for (int sb = 0; sb < M; sb += 64) {
                     if (!(groups >> ((sb >> 6) & 63) & 1)) continue;   // (P[t] is read below only where a read of s has an alignment in t: none in this group)
                     int t = sb + lane, num;
-                    double sc = dev_fast_score_w(R, S, T, c_lo, r0, M, s, (t < M && t != s) ? t : -1, improper, sLr, sFl, sLap, &num, 0, (int*)0, staged);
-                    if (t < M) T.P[t] = t == s ? 0.0 : pow(10.0, sc);
+                    double sc = dev_fast_score_w(R, S, T, H, c_lo, r0, M, s, (t < M && t != s) ? t : -1, improper, sLr, sFl, sLap, &num, 0, (int*)0, staged);
+                    if (t < M) H.P[t] = t == s ? 0.0 : pow(10.0, sc);
                 }
                 WAVE_SYNC();
                 RFA_PROF(8)
-                for (int k = lane; k < T.alen[s]; k += 64) {
-                    int a = T.act_store[T.aoff[s] + k], lr = S.cand_read[c_lo + a] - r0;
+                for (int k = lane; k < H.alen[s]; k += 64) {
+                    int a = H.act_store[H.aoff[s] + k], lr = S.cand_read[c_lo + a] - r0;
                     double sum = S.sum_move[c_lo + a];
                     const u64 mine = M > 64 && M <= 64 * 64 ? T.dk0[lr] : ~0ull;   // (the read's own groups: elsewhere its row of the table is empty)
                     for (int t0 = 0; t0 < M; t0 += 8) {   // (eight table entries read at a time; the sums in the molecules' order, as written)
@@ -1320,7 +1429,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                         for (int u = 0; u < 8; ++u) q8[u] = t0 + u < M ? T.bestT[(size_t)lr * M + t0 + u] : -1;
 #pragma unroll
                         for (int u = 0; u < 8; ++u)
-                            if (t0 + u != s && q8[u] >= 0) sum += T.P[t0 + u];
+                            if (t0 + u != s && q8[u] >= 0) sum += H.P[t0 + u];
                     }
                     S.sum_move[c_lo + a] = sum;
                 }
@@ -1328,26 +1437,27 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 RFA_PROF(2)
             }
             RFA_PROF(8)
+            RFA_FENCE()
             // ---- updateAlignmentsMoleculeStatus: confidences, differences, active molecules ----
             for (int m = lane; m < M; m += 64) {
-                double conf = (double)T.alen[m] / (double)T.nbest[m];
+                double conf = (double)H.alen[m] / (double)H.nbest[m];
                 int soft = 0, diffs = 0;
-                for (int k = 0; k < T.alen[m]; ++k) {
-                    int a = T.act_store[T.aoff[m] + k];
+                for (int k = 0; k < H.alen[m]; ++k) {
+                    int a = H.act_store[H.aoff[m] + k];
                     if (R.soft_clipped[c_lo + a] > 0) soft++;
                     diffs += R.mismatches[c_lo + a];
                 }
-                double diff = (double)diffs / (double)T.alen[m];
-                for (int k = 0; k < T.alen[m]; ++k) {
-                    int a = T.act_store[T.aoff[m] + k];
+                double diff = (double)diffs / (double)H.alen[m];
+                for (int k = 0; k < H.alen[m]; ++k) {
+                    int a = H.act_store[H.aoff[m] + k];
                     S.mol_conf[c_lo + a] = conf; S.mol_diff[c_lo + a] = diff;
                 }
-                T.mflag[m] = (T.alen[m] - soft > 4 && conf > 0.1) ? 1 : 0;
+                H.mflag[m] = (H.alen[m] - soft > 4 && conf > 0.1) ? 1 : 0;
             }
             WAVE_SYNC();
             for (int i = lane; i < NCf; i += 64) {
                 int a = T.plist[i], m = S.molecule_id[c_lo + a];
-                if (m != -1) S.active_molecule[c_lo + a] = (uint8_t)T.mflag[m];
+                if (m != -1) S.active_molecule[c_lo + a] = (uint8_t)H.mflag[m];
             }
             WAVE_SYNC();
         }
@@ -1358,11 +1468,11 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             double part = 0.0;
             if (do_rfa && M > 0) {
                 for (int m = 0; m < M; ++m) {
-                    const int al = T.alen[m], ao = T.aoff[m];
-                    if (T.mflag[m]) {
+                    const int al = H.alen[m], ao = H.aoff[m];
+                    if (H.mflag[m]) {
                         i64 smallest = 0x7fffffffffffffffll, biggest = -1;
                         for (int k = lane; k < al; k += 64) {
-                            i64 p = R.pos[c_lo + T.act_store[ao + k]];
+                            i64 p = R.pos[c_lo + H.act_store[ao + k]];
                             if (p > biggest) biggest = p;
                             if (p < smallest) smallest = p;
                         }
@@ -1374,7 +1484,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                         if (lane == 0 && biggest >= smallest) part += (double)(biggest - smallest) + 1000.0;
                     } else {
                         for (int k = lane; k < al; k += 64) {
-                            i64 g = c_lo + T.act_store[ao + k];
+                            i64 g = c_lo + H.act_store[ao + k];
                             part += (double)(R.aend[g] - R.pos[g]) * 2.0;
                         }
                     }
@@ -1386,6 +1496,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         WAVE_SYNC();
         double lmp = shd[0];
         RFA_PROF(9)
+        RFA_FENCE()
         // ---- per read: link active mates (lariat.go:892-900).  Done for all reads before any scoring that reads mate links. ----
         for (int r = lane; r < nR; r += 64) {
             i64 act = -1;
@@ -1416,6 +1527,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         }
         WAVE_SYNC();
         RFA_PROF(10)
+        RFA_FENCE()
         for (int r = lane; r < nR; r += 64) {
             int gr = r0 + r, gm = r0 + (r ^ 1);
             i64 a0 = R.cand_off[gr], a1 = R.cand_off[gr + 1], m0 = R.cand_off[gm], m1 = R.cand_off[gm + 1];
@@ -1479,6 +1591,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         }
         WAVE_SYNC();
         RFA_PROF(11)
+        RFA_FENCE()
 #ifdef LH_RA_HIST
         if (lane == 0) {   // barcodes by log2 of the time k_rfa spent on them (10 ns ticks), and by candidates
             const unsigned long long dt_ = (unsigned long long)wall_clock64() - bc_t0_;

@@ -80,6 +80,8 @@ struct lh_context {
     bool dl_pending = false, dl_split = false; std::function<int(lh_result**)> dl_finish;
     int sel_slot = 0;
     HostPeek* h_peek = nullptr;   // page-locked, device-writable: small read-backs inside lh_align_resident (lh_workspace.h)
+    bool rfa_merge_big = false;    // this batch: k_rfa_order put the big barcodes in front of the rest list (no first-tier slabs to route them to); rfa_prologue decides, rfa_run follows
+    i64 rfa_cls[4] = {0, 0, 0, 0}; // lh_last_rfa_classes: the last batch's big, rest and small barcodes as k_rfa_order listed them, and those the small instance turned away
     bool ext_hint_valid = false;   // h_peek->prev_wave_reads holds a previous batch's count
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     i64 cap_pairs = 0, cap_reads = 0, cap_bases = 0, pool_cap = 0, regpool_cap = 0, cap_bc = 0;
@@ -865,7 +867,7 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
     if (!c->resident) return set_err(LH_E_ARG, "no batch resident: call lh_batch_upload first");
     if (opts->abi_version != LH_ABI_VERSION) return set_err(LH_E_ARG, "lh_opts.abi_version does not match LH_ABI_VERSION (use lh_opts_init)");
-    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
+    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES | LH_F_RFA_SLAB)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
     HIPCHK(hipSetDevice(c->idx->device));
     {
         std::vector<void*> fl;

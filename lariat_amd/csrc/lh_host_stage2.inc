@@ -681,8 +681,12 @@ static RfaTier rfa_tier(const lh_context* c, int k, bool post) {
     if (k == RFA_LAST) return {c->d_slab2, c->slab2_bytes, c->grid_rfa2, post ? &n->post_last_next : &n->last_next};
     return {c->d_slab_mid[k], c->slab_mid_bytes[k], c->grid_rfa_mid[k], post ? &n->tier[k].post_next : &n->tier[k].next};
 }
+static void launch_rfa_small(lh_context* c, const DOpts& o, const RfaTier& T, hipStream_t st, RfaList in, RfaList out) {
+    LH_LAUNCH(k_rfa<1>, T.grid, 64, st, c->idx->d, o, c->b.n_bc, c->b.bc_pair_off, c->b.bc_do_rfa, c->b.name_seed, c->b.cen_start, c->b.cen_end, c->R, c->S, c->cand_cap, T.slab, T.bytes,
+              c->d_status, T.next, (const int32_t*)in.list, (const int32_t*)in.count, out.list, out.count, c->d_rfa_hr, &c->d_bc_next->heavy_reads, c->d_bc_lmp);
+}
 static void launch_rfa(lh_context* c, const DOpts& o, const RfaTier& T, hipStream_t st, RfaList in, RfaList out) {
-    LH_LAUNCH(k_rfa, T.grid, 64, st, c->idx->d, o, c->b.n_bc, c->b.bc_pair_off, c->b.bc_do_rfa, c->b.name_seed, c->b.cen_start, c->b.cen_end, c->R, c->S, c->cand_cap, T.slab, T.bytes,
+    LH_LAUNCH(k_rfa<0>, T.grid, 64, st, c->idx->d, o, c->b.n_bc, c->b.bc_pair_off, c->b.bc_do_rfa, c->b.name_seed, c->b.cen_start, c->b.cen_end, c->R, c->S, c->cand_cap, T.slab, T.bytes,
               c->d_status, T.next, (const int32_t*)in.list, (const int32_t*)in.count, out.list, out.count, c->d_rfa_hr, &c->d_bc_next->heavy_reads, c->d_bc_lmp);
 }
 static void launch_rfa_post(lh_context* c, const DOpts& o, const RfaTier& T, hipStream_t st, RfaList in, RfaList out) {
@@ -708,11 +712,14 @@ static int rfa_cascade(lh_context* c, const DOpts& o, bool post, RfaList in, i64
     return LH_OK;
 }
 
+// the first tier has slabs (an earlier batch needed them): the barcodes that cannot fit a regular slab start there at once, beside the first launch
+static bool rfa_routes_big(const lh_context* c) { return c->slab_mid_bytes[0] && c->d_slab_mid[0] && c->grid_rfa_mid[0] > 0; }
 // K8's prologue: the defaults of the inference columns and the order in which the barcode programs take their barcodes.  Both read the candidate offsets alone
 static void rfa_prologue(lh_context* c, hipStream_t st) {
     const RfaOrder ord(c->d_rfa_order, (size_t)c->cap_bc);
+    c->rfa_merge_big = !(c->flags & LH_F_RFA_SLAB) && !rfa_routes_big(c);
     LH_LAUNCH(k_rfa_init, 4096, 256, st, c->b.n_reads, c->R, c->S, c->cand_cap);
-    LH_LAUNCH(k_rfa_order, 1, 256, st, c->b.n_bc, (const int32_t*)c->b.bc_pair_off, c->R, ord.all, ord.big, ord.rest, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
+    LH_LAUNCH(k_rfa_order, 1, 256, st, c->b.n_bc, (const int32_t*)c->b.bc_pair_off, c->R, ord.all, ord.big, ord.rest, (c->flags & LH_F_RFA_SLAB) ? (int32_t*)nullptr : ord.small, c->rfa_merge_big ? 1 : 0, ord.n_all, c->slab_bytes, c->idx->d.n_contigs + 2);
 }
 
 static int rfa_run(lh_context* c, const DOpts& o, int& t) {
@@ -735,7 +742,7 @@ static int rfa_run(lh_context* c, const DOpts& o, int& t) {
     {
         // the first tier has slabs (an earlier batch needed them): the barcodes that cannot fit a regular slab start there at once, on a second stream, beside the first launch;
         // what they leave goes to the list the tier's own launch leaves its overflow in.  No slabs yet: the first launch sees every barcode and turns those away, as before
-        const bool pre = c->slab_mid_bytes[0] && c->d_slab_mid[0] && c->grid_rfa_mid[0] > 0;
+        const bool pre = rfa_routes_big(c);
         RfaList ovf{c->d_rfa_ovf, &ctr->n_ovf};
         const RfaList routed_ovf{RfaOvfMid(c->d_rfa_ovf_mid, (size_t)c->cap_bc).rfa[0], &ctr->tier[0].n_ovf};
         if (pre) {
@@ -746,12 +753,24 @@ static int rfa_run(lh_context* c, const DOpts& o, int& t) {
             launch_rfa(c, o, routed, c->aux[0], big, routed_ovf);
             HIPCHK(hipEventRecord(c->ev_join[0], c->aux[0]));
         }
-        launch_rfa(c, o, rfa_tier(c, RFA_REGULAR, false), c->stream, pre ? rest : all, ovf);
+        if (c->flags & LH_F_RFA_SLAB) launch_rfa(c, o, rfa_tier(c, RFA_REGULAR, false), c->stream, pre ? rest : all, ovf);   // every barcode through the regular instance (no small list)
+        else {
+            // (r13) the small barcodes through the small instance, on the regular slabs; what it turns away (more molecules than its on-chip tables hold) joins the
+            // rest list, whose launch follows on the same slabs and reads the list's length when it starts: no look from the host in between.  Without first-tier
+            // slabs k_rfa_order has put the big barcodes in front of that list (rfa_merge_big), to be turned away into ovf as before
+            RfaTier sm = rfa_tier(c, RFA_REGULAR, false);
+            sm.next = &ctr->small_next;
+            launch_rfa_small(c, o, sm, c->stream, RfaList{ord.small, ord.n_small}, rest);
+            launch_rfa(c, o, rfa_tier(c, RFA_REGULAR, false), c->stream, rest, ovf);
+        }
         if (pre) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
         i64 listed = 0;
         LH_LAUNCH(k_peek_i32, 1, 1, c->stream, (const int32_t*)ord.n_big, &c->h_peek->rfa_routed);   // (read with the list's length below: one synchronisation)
+        LH_LAUNCH(k_peek_rfa, 1, 1, c->stream, (const int32_t*)ord.n_all, &c->h_peek->rfa_classes);
         { int rc = rfa_list_len(c, ovf.count, &listed); if (rc) return rc; }
         const i64 n_routed = c->h_peek->rfa_routed;
+        c->rfa_cls[0] = n_routed; c->rfa_cls[2] = c->h_peek->rfa_classes & 0xffffffffll; c->rfa_cls[3] = c->h_peek->rfa_classes >> 32;
+        c->rfa_cls[1] = (i64)c->b.n_bc - c->rfa_cls[0] - c->rfa_cls[2];
         int k_first = 0;
         if (pre && listed == 0) {   // nothing for the first tier's own launch: what the routed barcodes left there is the next tier's list
             ovf = routed_ovf;

@@ -168,6 +168,14 @@ int lh_last_rounds(lh_context* c, int32_t lane, lh_round_info* out) {
     return LH_OK;
 }
 
+// K8's classes in the first pipeline's last run (a batch in rounds or lanes: its last part there)
+int lh_last_rfa_classes(lh_context* c, int64_t* out) {
+    if (!c || !out) return set_err(LH_E_ARG, "lh_last_rfa_classes: null argument");
+    if (!c->ran_inference) return set_err(LH_E_ARG, "lh_last_rfa_classes: call lh_align_resident with run_inference first");
+    for (int i = 0; i < 4; ++i) out[i] = c->rfa_cls[i];
+    return LH_OK;
+}
+
 // part behind acc (the first part becomes acc): merged into a new result, and both are freed whatever the outcome.  The rounds' parts and the lanes' fold this way
 static int merge_into(lh_result*& acc, lh_result* part) {
     if (!acc) { acc = part; return LH_OK; }

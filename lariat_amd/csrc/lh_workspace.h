@@ -87,7 +87,8 @@ struct RfaCounters {
         int32_t post_next, post_n_ovf;   // k_rfa_post: the same
     } tier[2];
     int32_t routed_next;      // work counter of the first tier's launch for the barcodes routed there up front (its overflow: tier[0].n_ovf)
-    int32_t unused[7];
+    int32_t small_next;       // work counter of the small instance's launch
+    int32_t unused[6];
 };
 static_assert(sizeof(RfaCounters) == 24 * sizeof(int32_t) && offsetof(RfaCounters, tier) == 8 * sizeof(int32_t) && offsetof(RfaCounters, routed_next) == 16 * sizeof(int32_t), "RfaCounters");
 
@@ -107,7 +108,7 @@ struct HostPeek {
     i64 prev_wave_reads;
     i64 rfa_listed;   // K8: the length of an overflow list (rfa_list_len)
     i64 rfa_routed;   // K8: the barcodes routed to the first tier up front (read with rfa_listed: one synchronisation)
-    i64 unused;
+    i64 rfa_classes;  // K8: k_peek_rfa's word (read with rfa_listed too): barcodes listed as small, and << 32 those the small instance turned away
 };
 static_assert(offsetof(HostPeek, one) == 0 && offsetof(HostPeek, k1.seeds) == 0 && offsetof(HostPeek, k1.big_asked) == 8, "k_peek_i64_i32: dst_host[0], [1]");
 static_assert(offsetof(HostPeek, k6.total) == 0 && offsetof(HostPeek, k6.padded) == 8 && offsetof(HostPeek, k6.listed) == 16 && offsetof(HostPeek, k6.n_long) == 24, "k_resc_offsets: peek_host[0 .. 3]");
@@ -175,12 +176,12 @@ struct RegsTmpLists {
 };
 static_assert(sizeof(DReg) >= 2 * sizeof(int32_t), "two lists in the region scratch");
 static_assert(sizeof(DReg) >= 4 * sizeof(int32_t), "four lists in the region scratch");
-// lh_context::d_rfa_order, k_rfa_order's output: three barcode lists, largest first, and their lengths
+// lh_context::d_rfa_order, k_rfa_order's output: four barcode lists, largest first, and their lengths
 struct RfaOrder {
-    static size_t ints(size_t cap_bc) { return 3 * (cap_bc + 4) + 4; }
-    int32_t *all, *big, *rest;         // every barcode; those whose tables cannot fit a regular slab; the others
-    int32_t *n_all, *n_big, *n_rest;   // k_rfa_order's counts[0 .. 2]
-    RfaOrder(int32_t* base, size_t cap_bc) : all(base), big(base + (cap_bc + 4)), rest(base + 2 * (cap_bc + 4)), n_all(base + 3 * (cap_bc + 4)), n_big(n_all + 1), n_rest(n_all + 2) {}
+    static size_t ints(size_t cap_bc) { return 4 * (cap_bc + 4) + 8; }
+    int32_t *all, *big, *rest, *small;           // every barcode; those whose tables cannot fit a regular slab; the others; those the small instance of k_rfa takes
+    int32_t *n_all, *n_big, *n_rest, *n_small;   // k_rfa_order's counts[0 .. 3] (counts[5]: n_rest as k_rfa_order wrote it; *n_rest itself grows by the barcodes the small instance turns away).  (rest has room for every barcode: the small instance appends those it turns away)
+    RfaOrder(int32_t* base, size_t cap_bc) : all(base), big(base + (cap_bc + 4)), rest(base + 2 * (cap_bc + 4)), small(base + 3 * (cap_bc + 4)), n_all(base + 4 * (cap_bc + 4)), n_big(n_all + 1), n_rest(n_all + 2), n_small(n_all + 3) {}
 };
 // lh_context::d_rfa_ovf_mid, the tiers' overflow lists: what tier k's launch of k_rfa / of k_rfa_post turns away (RfaCounters::tier[k] holds the lengths)
 struct RfaOvfMid {
