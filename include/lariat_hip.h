@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LH_ABI_VERSION 9
+#define LH_ABI_VERSION 10
 
 /* status codes */
 #define LH_OK 0
@@ -78,11 +78,12 @@ typedef struct lh_opts {
 #define LH_F_NO_SWEEP_FILTER 1u  /* K1 sweeps every interval like bwt_smem1a does (n_ext then counts every bwt_extend of the reference) */
 #define LH_F_EXT_WAVE 16u        /* K4 wave-per-read only */
 #define LH_F_EXT_SERIAL 32u      /* K4's rounds and wave-kernel launches one after the other on one stream (per-round timings) */
-#define LH_F_P2_TASKS 128u       /* K1 pass 2: a read's re-seeding calls shared by up to four lanes whatever the previous batch looked like (default: only after a repeat-rich batch) */
+#define LH_F_P2_TASKS 128u       /* K1 pass 2: every read's re-seeding calls shared by up to four lanes that scan and probe them (k_p2_tasks); default: the calls judged by k_p2_probe first, see LH_F_P2_SCAN */
 #define LH_F_RESCUE_FULL 256u     /* K6: every mate-rescue Smith-Waterman runs all rows of its window (default: the rows k_resc_cert proves sufficient, k_rescue3.h) */
 #define LH_F_SEED_LANE 512u       /* (ABI 7) K2: one lane per seed after a pass that names every seed slot's read (k_seed_owner + k_seed) and k_smem_fin sorting every read's intervals in memory before it; default: a 16-lane group per read that ranks its intervals itself, k_seed_grp */
 #define LH_F_TAIL_PASSES 1024u    /* (ABI 8) K5's lane form as a pass over every read after K4 (k_dedup_fast) and K8's prologue (k_rfa_init, k_rfa_order) after K7 on the main stream; default: a read's K5 on the lane that finishes its extension, the prologue beside K7 */
 #define LH_F_RFA_SLAB 2048u       /* (ABI 9) K8: every barcode through the regular instance of the barcode program, all its tables in the HBM slab (k_rfa<0>); default: the barcodes within LH_RFA_SM_* through the small instance, whose hot tables live in LDS (k_rfa<1>) */
+#define LH_F_P2_SCAN 4096u        /* (ABI 10) K1 pass 2 without the probe kernel: the state machine takes up every read, scans its intervals and probes each re-seeding call itself (after a repeat-rich batch: k_p2_tasks' shares); default: k_p2_probe judges every call in lockstep and pass 2 runs only the calls it lists */
 #define LH_F_CHAIN_WAVE 64u      /* K3: the reads a lane does not chain all go to the wave-per-seed kernel (k_chain), none to the cluster kernel (k_chain_cl) */
 
 /* how an index is made resident (lh_index_load / lh_index_from_arrays / lh_index_build_device); NULL = defaults */
@@ -350,6 +351,13 @@ int lh_last_rounds(lh_context* ctx, int32_t lane, lh_round_info* out);
  * instance's caps, those listed for the small instance (0 under LH_F_RFA_SLAB, and for a batch with more than an eighth of its barcodes beyond the caps), and of the
  * latter those the small instance turned away to the regular one (more molecules than its on-chip tables hold).  A test and measurement aid */
 int lh_last_rfa_classes(lh_context* ctx, int64_t* out /* [4] */);
+
+/* (ABI 10) what K1's pass-2 lister made of the re-seeding calls of the last lh_align_resident or stage dump (a batch in rounds or lanes: the first pipeline's last part):
+ * out[0 .. 3] = calls the probe dropped (no k-mer of the call's windows occurs twice: it cannot contribute), calls listed with the probe's answer, calls listed
+ * unprobed (the probe does not apply: windows not inside the SMEM, LH_F_NO_SWEEP_FILTER, an index without the text's bits), and reads listed as shares (more than
+ * four surviving calls, whose listed calls are not counted; under LH_F_P2_TASKS every read with a call).  All zero when no lister ran (LH_F_P2_SCAN after an
+ * ordinary batch).  A test and measurement aid */
+int lh_last_p2_calls(lh_context* ctx, int64_t* out /* [4] */);
 
 /* per-kernel timing of the last lh_align_resident (HIP events on the context's stream), ms; names are static strings.  After a run in rounds: per-kernel sums over the
  * rounds, plus "k1_discarded" (the K1 pass over the whole batch that found the overflow), "k_round_plan" and "k_batch_view" */

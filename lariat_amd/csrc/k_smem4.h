@@ -222,6 +222,18 @@ __global__ void __launch_bounds__(256) k_smem_first(DIndex ix, DOpts o, int n_re
 // BIG: the second chance of the reads whose intervals outgrew their LH_MAX_INTV regular slots (listed by k_big_collect): the same
 // passes again, over the list, into slab slots of LH_BIG_INTV intervals (BWA's interval vector grows; no read is refused for it).
 struct K1Big { const int32_t* list; const int32_t* count; const int32_t* slot; DIntv* slab; const K1Resume* resume; };   // slot[r]: the read's big-slab slot, -1: none; slab: 2 x LH_BIG_INTV per slot (unsorted | sorted); !BIG pass 1: list / count / resume = the reads k_smem_first left, and where
+// pass 2's list (k_p2_probe, k_p2_tasks; P2TASK in k_smem_pass): 64-bit entries, the read in the low 27 bits, then the kind.
+//   a call:  xm (8 bits: where bwt_smem1 starts) | min_intv (4) | pbits (LH_BLOOM_K = 19: the probe's answer) | LH_P2E_UNPROBED: the probe did not apply, pbits is 0 and no answer
+//   a share: LH_P2E_SHARE | j << 2 | m - 1 (4 bits): the lane scans the read's intervals and makes every m-th of its calls from the j-th on, probing each itself
+#define LH_P2E_READ ((1ull << 27) - 1)
+#define LH_P2E_SHARE (1ull << 27)
+#define LH_P2E_TASK 28
+#define LH_P2E_XM 28
+#define LH_P2E_MIN 36
+#define LH_P2E_PBITS 40
+#define LH_P2E_UNPROBED (1ull << 59)
+#define LH_P2_MAX_MIN_INTV 15   // what the entry's min_intv field holds: split_width + 1 beyond it keeps every read on share entries
+static_assert(LH_BLOOM_K <= 19 && LH_MAXLEN < 256, "a call entry: 8 bits of position, 19 of probe");
 // ---- request trace of pass 1 (development aid, -DLH_K1_TRACE: tools/k1_trace.py).  Every memory request of the state machine — table, address, bytes — is
 // appended to the lane's own sequence (entry k of lane t at trace[k * T + t]); k_k1_replay then issues the same sequences with the same launch geometry and
 // nothing else: each lane one request per turn, the next one only when the last has landed (what the state machine's turn structure does), no bookkeeping.
@@ -287,7 +299,9 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
     // after every other lane had finished.  With a task list (k_p2_tasks: big.list / big.count) a read's calls are dealt out to up to LH_P2_SPLIT lanes; what
     // they emit goes to the read's interval slots through an atomic counter, in whatever order — k_smem_fin sorts the intervals by position, and two
     // intervals with equal positions are the same interval.  Reads without such an SMEM are not listed at all.
-    const bool P2TASK = PASS == 2 && !BIG && big.list != nullptr;
+    // PASS 2 BY CALLS (r14).  The list's other kind of entry is ONE call that k_p2_probe has already judged: the read, the call's start, its min_intv and the probe's
+    // bits (LH_P2E_*).  The lane that takes it stages the read and starts the call: no interval is read, no probe made.  Both kinds emit through the read's counter.
+    const bool P2TASK = PASS == 2 && !BIG && big.list != nullptr;   // (then big.list holds 64-bit entries)
     int task_k = 0;
     // PASS 3 BY TEXT (with a dense suffix array).  A walk of bwt_seed_strategy1 from x ends at the first length L >= min_seed_len + 1
     // where the match occurs fewer than max_mem_intv times.  If [x, x + Lw), Lw = min_seed_len + 1, lies inside a UNIQUE SMEM of the read
@@ -592,6 +606,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             }
             i64 off = 0;
             int ln = 0, rr = -1;
+            u64 p2e = 0;   // pass 2 over a list: the entry this lane took
             if (st == S4_FETCH) {
 #ifdef LH_EMU
                 int idx = chunk_next + lanes_below(need, lane);
@@ -601,8 +616,8 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
                 rr = idx < chunk_end ? idx : newbase + (idx - chunk_end);
                 if (rr >= n_reads) st = S4_DONE;
                 else {
-                    if (BIG || big.list) rr = big.list[rr];
-                    if (P2TASK) { task_k = rr & 15; rr >>= 4; }   // pass 2 by tasks: (read, j << 2 | m - 1): every m-th of the read's re-seeding calls, from the j-th on
+                    if (P2TASK) { p2e = ((const u64*)big.list)[rr]; rr = (int)(p2e & LH_P2E_READ); }
+                    else if (BIG || big.list) rr = big.list[rr];
                     off = seq_off[rr]; ln = (int)(seq_off[rr + 1] - off);
                 }
             }
@@ -641,7 +656,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
                 K1_REQ(K1T_READS, seq_off + rr, 16)
                 if (len > LH_MAXLEN) { rst |= LH_ST_TOO_LONG; len = 0; }
                 out = BIG ? big.slab + (size_t)big.slot[r] * (2 * LH_BIG_INTV) : intv_out + (size_t)r * LH_MAX_INTV;
-                if (!DO1) { on = n_intv[r]; rst |= status[r]; }   // continue behind the intervals of the earlier passes
+                if (!DO1 && !P2TASK) { on = n_intv[r]; rst |= status[r]; }   // continue behind the intervals of the earlier passes (over a list: slots from the read's counter, new status bits by atomicOr)
                 if (len >= o.min_seed_len) { x = 0; st = DO1 ? S4_P1_SCAN : DO2 ? S4_P2_NEXT : S4_P3_SCAN; }
                 else st = S4_READ_DONE;
                 if (DO1 && !BIG && big.resume) {   // k_smem_first made the read's first call: its interval (if any) is stored, the calls go on from x
@@ -662,7 +677,12 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
                     }
                     if (UE0 > US0) st = S4_P3_PREP;
                 }
-                if (DO2 && st == S4_P2_NEXT) {   // the long, rare SMEMs among pass 1's intervals (EMIT_MEM's test)
+                if (DO2 && st == S4_P2_NEXT && P2TASK && !(p2e & LH_P2E_SHARE)) {   // a call k_p2_probe listed: straight to START_SMEM1, as S4_P2_NEXT / S4_P2_PROBE3 would have sent it
+                    x = (int)(p2e >> LH_P2E_XM) & 0xff; min_intv = (int)(p2e >> LH_P2E_MIN) & 0xf; pbits = (uint32_t)(p2e >> LH_P2E_PBITS) & ((1u << LH_BLOOM_K) - 1u);   // (unprobed: pbits = 0)
+                    todo |= TD_SMEM; st = S4_PENDING;
+                }
+                else if (DO2 && st == S4_P2_NEXT) {   // the long, rare SMEMs among pass 1's intervals (EMIT_MEM's test)
+                    task_k = (int)(p2e >> LH_P2E_TASK) & 15;   // a share entry, j << 2 | m - 1: every m-th of the read's re-seeding calls, from the j-th on
                     const int on1 = P2TASK ? big.slot[r] : on;   // (by tasks: the read's other calls may have emitted already: the SMEMs to re-seed inside are PASS 1's — k_p2_tasks noted how many there are)
                     int ord = 0;
                     for (int k = 0; k < on1; ++k) {
@@ -1185,11 +1205,14 @@ __global__ void __launch_bounds__(256) k_k1_trace_hist(const u64* __restrict__ t
 #endif
 
 // pass 2's tasks (see P2TASK): a read with c long, rare SMEMs among pass 1's intervals (mem_collect_intv's test: length >= min_seed_len * split_factor, at most
-// split_width occurrences) is listed m = min(c, LH_P2_SPLIT) times, entry read << 4 | j << 2 | m - 1: the lane that takes it makes the read's j-th, (j + m)-th
+// split_width occurrences) is listed m = min(c, LH_P2_SPLIT) times, as share entries (LH_P2E_SHARE): the lane that takes one makes the read's j-th, (j + m)-th
 // ... re-seeding call.  One thread per read; at most LH_P2_SPLIT entries per read: the list never overflows its LH_P2_SPLIT x n_reads slots.
 #define LH_P2_SPLIT 4
-__global__ void __launch_bounds__(256) k_p2_tasks(DOpts o, int n_reads, const DIntv* __restrict__ intv, const int32_t* __restrict__ n_intv, int32_t* __restrict__ tasks,
-                                                   int32_t* __restrict__ n_tasks, int32_t* __restrict__ n_pass1) {
+// what the listers report (lh_last_p2_calls): LH_CTR_SLOTS copies on separate 128-B lines, as DCounters
+struct __attribute__((aligned(128))) P2Calls { u64 dropped, probed, unprobed, shares, pad_[12]; };
+__device__ __forceinline__ u64 p2_share_entry(int r, int j, int m) { return (u64)(uint32_t)r | LH_P2E_SHARE | (u64)(j << 2 | (m - 1)) << LH_P2E_TASK; }
+__global__ void __launch_bounds__(256) k_p2_tasks(DOpts o, int n_reads, const DIntv* __restrict__ intv, const int32_t* __restrict__ n_intv, u64* __restrict__ tasks,
+                                                   int32_t* __restrict__ n_tasks, int32_t* __restrict__ n_pass1, P2Calls* __restrict__ calls) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
     int m = 0;
     if (r < n_reads) {
@@ -1204,11 +1227,106 @@ __global__ void __launch_bounds__(256) k_p2_tasks(DOpts o, int n_reads, const DI
     }
     const int incl = wave_scan_add_i32(m);
     const int tot = wave_readlane(incl, 63);
+    const int n_sh = __popcll(__ballot(m > 0));
+    int basep = 0;
+    if (lane == 0 && tot) { basep = atomicAdd(n_tasks, tot); atomicAdd(&LH_CTR(calls)->shares, (u64)n_sh); }
+    basep = wave_readlane(basep, 0);
+    for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = p2_share_entry(r, j, m);
+}
+// PASS 2'S PROBE IN LOCKSTEP (r14), one thread per read.  What S4_P2_NEXT and the probe states do before a re-seeding call starts is the same short program for every
+// read — the read's pass-1 intervals, the middle base, one text position, two words of rep_t — and in unique sequence it ends most calls before they begin (the probe
+// finds no repeated k-mer: the call cannot contribute).  The state machine paid a staged query and four dependent turns for each of them.  Here the program runs in
+// plain loops, a read's loads issued together, and only what survives is listed: a call with the probe's answer in its entry (or marked unprobed where the probe does
+// not apply: windows not inside the SMEM, no filter, no rep_t), which pass 2 starts without reading an interval.  A read with more than LH_P2_SPLIT surviving calls
+// is listed as LH_P2_SPLIT share entries instead (k_p2_tasks' form: the list stays within its LH_P2_SPLIT x n_reads slots, and a repeat-rich read's calls still
+// spread over lanes).  The tests are S4_P2_NEXT's, in its order; the entries of a block's reads are appended with one atomicAdd per wave.
+__global__ void __launch_bounds__(256) k_p2_probe(DIndex ix, DOpts o, int n_reads, const uint8_t* __restrict__ seq, const i64* __restrict__ seq_off, const DIntv* __restrict__ intv,
+                                                   const int32_t* __restrict__ n_intv, u64* __restrict__ tasks, int32_t* __restrict__ n_tasks, int32_t* __restrict__ n_pass1,
+                                                   P2Calls* __restrict__ calls) {
+    __shared__ u64 ent[LH_P2_SPLIT * 256];   // entry j of thread t at ent[j * 256 + t]
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
+    const bool probe = ix.bloom1 != nullptr && ix.rep_t != nullptr && o.min_seed_len >= LH_BLOOM_K;   // (k_smem_pass: filt && ix.rep_t)
+    const int split_len = (int)(o.min_seed_len * o.split_factor + .499);
+#ifdef LH_P2_PROBE_WEAK   // test builds only: a probe that overlooks the last window (the tests' planted k-mer there must then go missing)
+    const u64 pmask = (1ull << (LH_BLOOM_K - 1)) - 1;
+#else
+    const u64 pmask = (1ull << LH_BLOOM_K) - 1;
+#endif
+    int m = 0, n_drop = 0, n_prob = 0, n_unpr = 0, share = 0;
+    if (r < n_reads) {
+        const int on = n_intv[r] < LH_MAX_INTV ? n_intv[r] : LH_MAX_INTV;
+        n_pass1[r] = on;
+        const uint4* const iv = (const uint4*)(intv + (size_t)r * LH_MAX_INTV);   // an interval: (x0, x1), (x2, info)
+        const i64 off = seq_off[r];
+        for (int k0 = 0; k0 < on; k0 += 4) {   // four intervals at a time: each step's loads are in flight together
+            uint4 lo[4], hi[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                lo[q] = hi[q] = uint4{0, 0, 0, 0};
+                if (k0 + q < on) { lo[q] = iv[2 * (k0 + q)]; hi[q] = iv[2 * (k0 + q) + 1]; }
+            }
+            bool call[4], in[4];
+            int xm[4], w0[4];
+            uint32_t base[4];
+            u64 pos[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int s = (int)hi[q].w, e = (int)hi[q].z;
+                const u64 x0 = (u64)lo[q].x | (u64)lo[q].y << 32, x2 = (u64)hi[q].x | (u64)hi[q].y << 32;
+                call[q] = k0 + q < on && e - s >= split_len && x2 <= (u64)o.split_width;   // long and rare
+                xm[q] = (s + e) >> 1; w0[q] = xm[q] - (LH_BLOOM_K - 1) - s;
+                in[q] = call[q] && probe && w0[q] >= 0 && xm[q] + LH_BLOOM_K <= e;   // the windows lie inside the SMEM
+                base[q] = 4; pos[q] = x0 & ~LH_POSF;
+                if (call[q]) base[q] = seq[off + xm[q]];
+                if (in[q] && !(x0 & LH_POSF)) pos[q] = ix.sa[x0];   // stored as rows: the first row's occurrence
+            }
+            u64 b0[4], b1[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                call[q] = call[q] && base[q] <= 3;   // bwt_smem1a returns at once on an ambiguous base: no call
+                in[q] = in[q] && call[q];
+                b0[q] = b1[q] = 0; pos[q] += (u64)w0[q];   // the first window's text position
+                if (in[q]) { b0[q] = ix.rep_t[pos[q] >> 6]; b1[q] = ix.rep_t[(pos[q] >> 6) + 1]; }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (!call[q]) continue;
+                const uint32_t sh = (uint32_t)(pos[q] & 63);
+                const u64 pbits = (sh ? (b0[q] >> sh) | (b1[q] << (64 - sh)) : b0[q]) & pmask;
+                if (in[q] && !pbits) { ++n_drop; continue; }
+                if (in[q]) ++n_prob; else ++n_unpr;
+                const u64 min_intv = ((u64)hi[q].x | (u64)hi[q].y << 32) + 1;
+                if (m < LH_P2_SPLIT)
+                    ent[m * 256 + threadIdx.x] = (u64)(uint32_t)r | (u64)xm[q] << LH_P2E_XM | min_intv << LH_P2E_MIN | (in[q] ? pbits << LH_P2E_PBITS : LH_P2E_UNPROBED);
+                ++m;
+            }
+        }
+        if (m > LH_P2_SPLIT) { share = 1; m = LH_P2_SPLIT; n_prob = n_unpr = 0; }   // (a share's lane judges its calls again: only the dropped ones count here)
+    }
+    const int incl = wave_scan_add_i32(m);
+    const int tot = wave_readlane(incl, 63);
     int basep = 0;
     if (lane == 0 && tot) basep = atomicAdd(n_tasks, tot);
     basep = wave_readlane(basep, 0);
-    for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = r << 4 | j << 2 | (m - 1);
+    for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = share ? p2_share_entry(r, j, m) : ent[j * 256 + threadIdx.x];
+    const int t_drop = wave_sum_i32(n_drop), t_prob = wave_sum_i32(n_prob), t_unpr = wave_sum_i32(n_unpr), t_sh = __popcll(__ballot(share));
+    if (lane == 0) {
+        if (t_drop) atomicAdd(&LH_CTR(calls)->dropped, (u64)t_drop);
+        if (t_prob) atomicAdd(&LH_CTR(calls)->probed, (u64)t_prob);
+        if (t_unpr) atomicAdd(&LH_CTR(calls)->unprobed, (u64)t_unpr);
+        if (t_sh) atomicAdd(&LH_CTR(calls)->shares, (u64)t_sh);
+    }
 }
+// the listers' counts in two words for the host: dropped | probed << 32, unprobed | shares << 32 (a read-out: each count modulo 2^32)
+__global__ void __launch_bounds__(64) k_peek_k1(const i64* __restrict__ seeds, const int32_t* __restrict__ big_asked, const P2Calls* __restrict__ calls, i64* __restrict__ dst_host) {
+    const P2Calls c = calls[LANE() & (LH_CTR_SLOTS - 1)];
+    const int d = wave_sum_i32((int)c.dropped), p = wave_sum_i32((int)c.probed), u = wave_sum_i32((int)c.unprobed), s = wave_sum_i32((int)c.shares);
+    if (LANE() == 0) {
+        dst_host[0] = *seeds; dst_host[1] = *big_asked;
+        dst_host[2] = (i64)((u64)(uint32_t)d | (u64)(uint32_t)p << 32); dst_host[3] = (i64)((u64)(uint32_t)u | (u64)(uint32_t)s << 32);
+    }
+}
+static_assert(LH_CTR_SLOTS == 64, "k_peek_k1: a lane per slot");
 __global__ void __launch_bounds__(256) k_p2_clamp(int n_reads, int32_t* __restrict__ n_intv) {   // (a read whose calls asked for more slots than it has: flagged by the call that was refused)
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n_reads && n_intv[r] > LH_MAX_INTV) n_intv[r] = LH_MAX_INTV;

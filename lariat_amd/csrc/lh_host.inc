@@ -102,7 +102,9 @@ struct lh_context {
     const uint32_t* q4 = nullptr;   // d_seq4 + 2 while the index has the 4-bit text (run_front)
     // K1
     DIntv* d_intv = nullptr; DIntv* d_big_slab = nullptr; int32_t *d_big_slot = nullptr, *d_big_list = nullptr; K1BigCounts* d_big_count = nullptr; int big_cap = 0, big_base = 0;   // reads with more than LH_MAX_INTV intervals (k_smem4.h BIG)
-    K1Resume* d_k1_resume = nullptr; int32_t *d_k1_todo = nullptr, *d_p2_tasks = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read->n_todo)
+    K1Resume* d_k1_resume = nullptr; int32_t* d_k1_todo = nullptr;   // k_smem_first's hand-over to the state machine (the count: d_next_read->n_todo)
+    u64* d_p2_tasks = nullptr; P2Calls* d_p2_calls = nullptr;   // pass 2's list (the count: d_next_read->n_p2_tasks) and what its lister counted, LH_CTR_SLOTS copies
+    i64 p2_cls[4] = {0, 0, 0, 0};   // lh_last_p2_calls: the last batch's re-seeding calls dropped, listed probed, listed unprobed, and its reads listed as shares
     int32_t *d_n_intv = nullptr, *d_seed_cnt = nullptr, *d_l_rep = nullptr, *d_status = nullptr;
     int32_t* d_fin_list = nullptr;   // the reads pass 3 leaves to k_smem_fin (the count: d_next_read->n_fin); the others' intervals K2 ranks itself
     // K2/K3
@@ -317,7 +319,7 @@ static int pipe_create(lh_index* idx, int64_t max_pairs, const lh_context_opts* 
     }
     DALLOC(g, c->d_intv, N * LH_MAX_INTV); DALLOC(g, c->d_n_intv, N);
     c->big_cap = c->co.big_slots > 0 ? c->co.big_slots : LH_MAX_INTV < 16 ? (int)N : (int)(N / 256 > 64 ? N / 256 : 64);   // (a test build with tiny regular slots sends most reads there)
-    DALLOC(g, c->d_k1_resume, N); DALLOC(g, c->d_k1_todo, N); DALLOC(g, c->d_p2_tasks, (size_t)LH_P2_SPLIT * N);
+    DALLOC(g, c->d_k1_resume, N); DALLOC(g, c->d_k1_todo, N); DALLOC(g, c->d_p2_tasks, (size_t)LH_P2_SPLIT * N); DALLOC(g, c->d_p2_calls, LH_CTR_SLOTS);
     DALLOC(c->big_mem, c->d_big_slab, (size_t)c->big_cap * 2 * LH_BIG_INTV); DALLOC(g, c->d_big_slot, N); DALLOC(c->big_mem, c->d_big_list, c->big_cap); DALLOC(g, c->d_big_count, 1);
     DALLOC(g, c->d_seed_cnt, N); DALLOC(g, c->d_l_rep, N); DALLOC(g, c->d_status, N); DALLOC(g, c->d_fin_list, N);
     {   // persistent-lane K1: 64 reads per wave in flight, as many waves as the device keeps resident (tunable for experiments)
@@ -517,10 +519,12 @@ static int smem_fin(lh_context* c, const DOpts& o, int N, bool listed) {
     return LH_OK;
 }
 
-// the batch's seed total and the reads that asked for a slot of the big slab, on the host (h_peek->k1)
+// the batch's seed total, the reads that asked for a slot of the big slab and pass 2's call counts, on the host (h_peek->k1)
 static int peek_seed_total(lh_context* c, int N) {
-    LH_LAUNCH(k_peek_i64_i32, 1, 1, c->stream, (const i64*)(c->d_seed_off + N), (const int32_t*)&c->d_big_count->asked, &c->h_peek->k1.seeds);   // (not a copy-engine transfer: those may be busy with the previous result / the next batch)
+    LH_LAUNCH(k_peek_k1, 1, 64, c->stream, (const i64*)(c->d_seed_off + N), (const int32_t*)&c->d_big_count->asked, (const P2Calls*)c->d_p2_calls, &c->h_peek->k1.seeds);   // (not a copy-engine transfer: those may be busy with the previous result / the next batch)
     HIPCHK(hipStreamSynchronize(c->stream));
+    const u64 dp = (u64)c->h_peek->k1.p2_drop_probed, us = (u64)c->h_peek->k1.p2_unprobed_shares;
+    c->p2_cls[0] = (i64)(dp & 0xffffffffu); c->p2_cls[1] = (i64)(dp >> 32); c->p2_cls[2] = (i64)(us & 0xffffffffu); c->p2_cls[3] = (i64)(us >> 32);
     return LH_OK;
 }
 
@@ -559,18 +563,28 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         { int rc = k1_trace_replay(c, trace, N, g4); if (rc) return rc; }
 #endif
         T_BEGIN("k_smem4_p2");
-        // the re-seeding calls as tasks: up to LH_P2_SPLIT lanes share a read's calls (k_smem4.h: P2TASK).  Worth its list when reads carry many such calls — reads on
-        // repeat copies: pass 2 45 -> 31 ms on the repeat input, 29 -> 20 with 5 % of the pairs there, but 4.7 -> 5.4 ms on unique sequence — so, like K4's choice
-        // of path and with the same sign (the wave-chained reads of the context's PREVIOUS batch), a choice of path and never of result
-        const bool p2_tasks = ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek->prev_wave_reads >= ext_long_min(N))) && N < (1 << 27);
+        // Pass 2 runs over a list (k_smem4.h: P2TASK).  By default k_p2_probe makes it: every re-seeding call judged in lockstep, the calls that can contribute listed one
+        // by one with the probe's answer, a read with more than LH_P2_SPLIT of them as shares.  LH_F_P2_TASKS: every read with a call as shares, up to LH_P2_SPLIT lanes
+        // scanning and probing a read's calls themselves (k_p2_tasks; pass 2 45 -> 31 ms on the repeat input, but 4.7 -> 5.4 ms on unique sequence).  LH_F_P2_SCAN: the
+        // sequence before the probe kernel — the state machine over every read, or k_p2_tasks after a repeat-rich batch (the wave-chained reads of the context's PREVIOUS
+        // batch, the sign K4 chooses its path by).  A choice of path and never of result.  (A list needs N < 2^27 and the call entry's four bits of min_intv.)
+        HIPCHK(hipMemsetAsync(c->d_p2_calls, 0, sizeof(P2Calls) * LH_CTR_SLOTS, c->stream));
+        const bool p2_list_ok = N < (1 << 27);
+        bool p2_probe = p2_list_ok && !(c->flags & (LH_F_P2_TASKS | LH_F_P2_SCAN)) && o.split_width < LH_P2_MAX_MIN_INTV;
+#ifdef LH_K1_TRACE
+        p2_probe = false;   // (the trace build's list-length histograms are the state machine's)
+#endif
+        const bool p2_tasks = p2_list_ok && !p2_probe && ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek->prev_wave_reads >= ext_long_min(N)));
         K1Big p2 = nobig;
-        if (p2_tasks) {
-            p2.list = c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo;   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
-            LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, &c->d_next_read->n_p2_tasks, c->d_k1_todo);
-        }
+        if (p2_probe || p2_tasks) { p2.list = (const int32_t*)c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo; }   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
+        if (p2_probe)
+            LH_LAUNCH(k_p2_probe, (N + 255) / 256, 256, c->stream, ix4, o, N, (const uint8_t*)c->b.seq, (const i64*)c->b.seq_off, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks,
+                      &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
+        else if (p2_tasks)
+            LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
         if (qw_small) smem_pass<2, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, p2);
         else smem_pass<2, false>(c, ix4, o, N, g4, p2);
-        if (p2_tasks) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
+        if (p2_probe || p2_tasks) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
         T_END();
 #ifdef LH_K1_TRACE
         { int rc = k1_trace_lens(c, trace); if (rc) return rc; }
@@ -867,7 +881,7 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
     if (!c->resident) return set_err(LH_E_ARG, "no batch resident: call lh_batch_upload first");
     if (opts->abi_version != LH_ABI_VERSION) return set_err(LH_E_ARG, "lh_opts.abi_version does not match LH_ABI_VERSION (use lh_opts_init)");
-    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES | LH_F_RFA_SLAB)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
+    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES | LH_F_RFA_SLAB | LH_F_P2_SCAN)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
     HIPCHK(hipSetDevice(c->idx->device));
     {
         std::vector<void*> fl;

@@ -176,6 +176,13 @@ int lh_last_rfa_classes(lh_context* c, int64_t* out) {
     return LH_OK;
 }
 
+// pass 2's calls as the lister of the first pipeline's last K1 counted them
+int lh_last_p2_calls(lh_context* c, int64_t* out) {
+    if (!c || !out) return set_err(LH_E_ARG, "lh_last_p2_calls: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = c->p2_cls[i];
+    return LH_OK;
+}
+
 // part behind acc (the first part becomes acc): merged into a new result, and both are freed whatever the outcome.  The rounds' parts and the lanes' fold this way
 static int merge_into(lh_result*& acc, lh_result* part) {
     if (!acc) { acc = part; return LH_OK; }

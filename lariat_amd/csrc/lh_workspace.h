@@ -52,7 +52,7 @@ struct K1Counters {
     int32_t pass[3];       // the three passes' read counters (k_smem_pass: the next read a lane takes)
     int32_t big_pass[3];   // the same for the second chance (k1_big_round)
     int32_t n_todo;        // reads k_smem_first left to pass 1: the length of lh_context::d_k1_todo
-    int32_t n_p2_tasks;    // pass 2's tasks (k_p2_tasks): the length of lh_context::d_p2_tasks
+    int32_t n_p2_tasks;    // pass 2's list (k_p2_probe, k_p2_tasks): the length of lh_context::d_p2_tasks
     int32_t n_fin;         // reads k_smem_p3_lock lists for k_smem_fin: the length of lh_context::d_fin_list
 };
 static_assert(sizeof(K1Counters) == 9 * sizeof(int32_t) && offsetof(K1Counters, big_pass) == 3 * sizeof(int32_t) && sizeof(K1Counters::big_pass) == 3 * sizeof(int32_t),
@@ -96,11 +96,11 @@ static_assert(sizeof(RfaCounters) == 24 * sizeof(int32_t) && offsetof(RfaCounter
 // Written by one-thread kernels (k_peek_*, k_resc_offsets), not by copy-engine transfers: those may be busy with the previous result or the next batch.  The host
 // reads a value after it has synchronised the stream the kernel ran on.
 struct HostPeek {
-    struct K1 { i64 seeds, big_asked; };
+    struct K1 { i64 seeds, big_asked, p2_drop_probed, p2_unprobed_shares; };
     struct K6 { i64 total, padded, listed, n_long; };
     union {   // the read-back of the moment; every one is consumed before the next is launched
         i64 one;   // k_peek_i32 / k_peek_i64: K4's queued jobs (ext_long_queue), the batch's candidates (stage2_run)
-        K1 k1;     // k_peek_i64_i32 (run_front): the batch's seeds; the reads that asked for a slot of the big slab
+        K1 k1;     // k_peek_k1 (run_front): the batch's seeds; the reads that asked for a slot of the big slab; pass 2's call counts, two to a word (k_smem4.h)
         K6 k6;     // k_resc_offsets (rescue_dir): jobs; their order array's padded length; listed pairs; those with long lists
     };
     // the one value that outlives a batch.  Written by stage2_run's last k_peek_i32 on the auxiliary stream (joined before the batch ends) and by nothing else;
@@ -110,7 +110,7 @@ struct HostPeek {
     i64 rfa_routed;   // K8: the barcodes routed to the first tier up front (read with rfa_listed: one synchronisation)
     i64 rfa_classes;  // K8: k_peek_rfa's word (read with rfa_listed too): barcodes listed as small, and << 32 those the small instance turned away
 };
-static_assert(offsetof(HostPeek, one) == 0 && offsetof(HostPeek, k1.seeds) == 0 && offsetof(HostPeek, k1.big_asked) == 8, "k_peek_i64_i32: dst_host[0], [1]");
+static_assert(offsetof(HostPeek, one) == 0 && offsetof(HostPeek, k1.seeds) == 0 && offsetof(HostPeek, k1.big_asked) == 8 && offsetof(HostPeek, k1.p2_drop_probed) == 16 && sizeof(HostPeek::K1) == 32, "k_peek_k1: dst_host[0 .. 3]");
 static_assert(offsetof(HostPeek, k6.total) == 0 && offsetof(HostPeek, k6.padded) == 8 && offsetof(HostPeek, k6.listed) == 16 && offsetof(HostPeek, k6.n_long) == 24, "k_resc_offsets: peek_host[0 .. 3]");
 static_assert(sizeof(HostPeek) == 64 && offsetof(HostPeek, prev_wave_reads) == 32, "HostPeek");
 
