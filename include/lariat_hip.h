@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LH_ABI_VERSION 10
+#define LH_ABI_VERSION 11
 
 /* status codes */
 #define LH_OK 0
@@ -84,6 +84,7 @@ typedef struct lh_opts {
 #define LH_F_TAIL_PASSES 1024u    /* (ABI 8) K5's lane form as a pass over every read after K4 (k_dedup_fast) and K8's prologue (k_rfa_init, k_rfa_order) after K7 on the main stream; default: a read's K5 on the lane that finishes its extension, the prologue beside K7 */
 #define LH_F_RFA_SLAB 2048u       /* (ABI 9) K8: every barcode through the regular instance of the barcode program, all its tables in the HBM slab (k_rfa<0>); default: the barcodes within LH_RFA_SM_* through the small instance, whose hot tables live in LDS (k_rfa<1>) */
 #define LH_F_P2_SCAN 4096u        /* (ABI 10) K1 pass 2 without the probe kernel: the state machine takes up every read, scans its intervals and probes each re-seeding call itself (after a repeat-rich batch: k_p2_tasks' shares); default: k_p2_probe judges every call in lockstep and pass 2 runs only the calls it lists */
+#define LH_F_P3_LAST 8192u        /* (ABI 11) K1 pass 3 behind pass 2, each with a lockstep kernel of its own (k_p2_probe, pass 2, k_p2_clamp, k_smem_p3_lock); default: one lockstep kernel behind pass 1 judges pass 2's calls and makes pass 3's walks (k_p23_lock), pass 2 appends behind it and k_p2_close ends the stage */
 #define LH_F_CHAIN_WAVE 64u      /* K3: the reads a lane does not chain all go to the wave-per-seed kernel (k_chain), none to the cluster kernel (k_chain_cl) */
 
 /* how an index is made resident (lh_index_load / lh_index_from_arrays / lh_index_build_device); NULL = defaults */
@@ -358,6 +359,11 @@ int lh_last_rfa_classes(lh_context* ctx, int64_t* out /* [4] */);
  * four surviving calls, whose listed calls are not counted; under LH_F_P2_TASKS every read with a call).  All zero when no lister ran (LH_F_P2_SCAN after an
  * ordinary batch).  A test and measurement aid */
 int lh_last_p2_calls(lh_context* ctx, int64_t* out /* [4] */);
+
+/* (ABI 11) the reads K1 listed for k_smem_fin in the last lh_align_resident or stage dump (a batch in rounds or lanes: the first pipeline's last part): those with more
+ * than 16 SMEM intervals or one above max_occ, whose intervals are sorted and counted in memory; every other read's K2 ranks itself.  *n = how many (0 on the paths
+ * that sort every read: LH_F_SEED_LANE, no pass 3), out[0 .. min(*n, cap) - 1] = their numbers in the part, in no order.  A test and measurement aid */
+int lh_last_fin_list(lh_context* ctx, int32_t* out, int64_t cap, int64_t* n);
 
 /* per-kernel timing of the last lh_align_resident (HIP events on the context's stream), ms; names are static strings.  After a run in rounds: per-kernel sums over the
  * rounds, plus "k1_discarded" (the K1 pass over the whole batch that found the overflow), "k_round_plan" and "k_batch_view" */

@@ -13,11 +13,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LARIAT_HIP_LIB") or os.path.join(_HERE, "_build", "liblariat_hip.so")
 
 LH_OK = 0
-LH_ABI_VERSION = 10
+LH_ABI_VERSION = 11
 LH_E_ARG, LH_E_IO, LH_E_HIP, LH_E_CAPACITY, LH_E_NODEVICE, LH_E_LIMIT = 1, 2, 3, 4, 5, 6
 # lh_opts.flags
 LH_REC_DEBUG_TAGS = 1
-LH_F_NO_SWEEP_FILTER, LH_F_EXT_WAVE, LH_F_EXT_SERIAL, LH_F_CHAIN_WAVE, LH_F_P2_TASKS, LH_F_RESCUE_FULL, LH_F_SEED_LANE, LH_F_TAIL_PASSES, LH_F_RFA_SLAB, LH_F_P2_SCAN = 1, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
+LH_F_NO_SWEEP_FILTER, LH_F_EXT_WAVE, LH_F_EXT_SERIAL, LH_F_CHAIN_WAVE, LH_F_P2_TASKS, LH_F_RESCUE_FULL, LH_F_SEED_LANE, LH_F_TAIL_PASSES, LH_F_RFA_SLAB, LH_F_P2_SCAN, LH_F_P3_LAST = 1, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
 LH_MAX_READ_LEN = 250
 
 c_i32p = C.POINTER(C.c_int32)
@@ -826,6 +826,16 @@ class Context:
         self.lib.check(self.lib.L.lh_last_p2_calls(self.h, out))
         return dict(dropped=int(out[0]), probed=int(out[1]), unprobed=int(out[2]), shares=int(out[3]))
 
+    def fin_list(self):
+        """lh_last_fin_list: the reads the last align or stage dump listed for k_smem_fin, sorted"""
+        L = self.lib.L
+        L.lh_last_fin_list.argtypes = [C.c_void_p, c_i32p, C.c_int64, C.POINTER(C.c_int64)]
+        n = C.c_int64()
+        self.lib.check(L.lh_last_fin_list(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(int(n.value), 1), dtype=np.int32)
+        self.lib.check(L.lh_last_fin_list(self.h, out.ctypes.data_as(c_i32p), len(out), C.byref(n)))
+        return np.sort(out[:int(n.value)])
+
     def stage_dump(self, batch=None, opts=None):
         opts = opts or self.lib.opts()
         if batch is not None:
@@ -1034,7 +1044,7 @@ EXPORTED_SYMBOLS = [
     "lh_ingest_open", "lh_ingest_next", "lh_ingest_batch_free", "lh_ingest_close", "lh_name_seed",
     "lh_records_text", "lh_records_text_ex", "lh_records_free", "lh_bam_open", "lh_bam_append", "lh_bam_set_flags", "lh_bam_close",
     "lh_index_free", "lh_index_build", "lh_context_create", "lh_context_free", "lh_align_barcodes", "lh_batch_upload", "lh_align_resident",
-    "lh_result_download", "lh_result_free", "lh_last_timings", "lh_last_rounds", "lh_last_rfa_classes", "lh_last_p2_calls", "lh_stage_dump_resident", "lh_stage_dump_free", "lh_get_seq", "lh_device_memory", "lh_diag_gosort", "lh_diag_gosort_split", "lh_diag_bitonic", "lh_diag_introsort", "lh_diag_random_read", "lh_diag_valu_rate", "lh_diag_rescue_sw", "lh_diag_go_rand", "lh_diag_rescue_dedup",
+    "lh_result_download", "lh_result_free", "lh_last_timings", "lh_last_rounds", "lh_last_rfa_classes", "lh_last_p2_calls", "lh_last_fin_list", "lh_stage_dump_resident", "lh_stage_dump_free", "lh_get_seq", "lh_device_memory", "lh_diag_gosort", "lh_diag_gosort_split", "lh_diag_bitonic", "lh_diag_introsort", "lh_diag_random_read", "lh_diag_valu_rate", "lh_diag_rescue_sw", "lh_diag_go_rand", "lh_diag_rescue_dedup",
     "lh_index_opts_init", "lh_context_opts_init", "lh_index_build_device", "lh_index_export", "lh_index_save", "lh_synth_genome", "lh_synth_reads", "lh_synth_write_fastq9", "lh_diag_index_check", "lh_batch_upload_slot", "lh_batch_select", "lh_bam_concat", "lh_reference_pack", "lh_index_set_holes", "lh_diag_index_digest", "lh_index_set_alt", "lh_index_alt", "lh_bam_set_level", "lh_bam_timings", "lh_result_download_begin", "lh_result_download_end", "lh_batch_stage_slot", "lh_host_alloc", "lh_host_free",
     "lh_bgzf_create", "lh_bgzf_free", "lh_bgzf_compress", "lh_bgzf_bound", "lh_bgzf_timings", "lh_bam_set_device",
     "lh_bam_set_device_records", "lh_bam_records_timings", "lh_diag_format_f6",

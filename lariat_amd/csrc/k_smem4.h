@@ -221,7 +221,8 @@ __global__ void __launch_bounds__(256) k_smem_first(DIndex ix, DOpts o, int n_re
 // fewer instructions per turn, fewer registers.
 // BIG: the second chance of the reads whose intervals outgrew their LH_MAX_INTV regular slots (listed by k_big_collect): the same
 // passes again, over the list, into slab slots of LH_BIG_INTV intervals (BWA's interval vector grows; no read is refused for it).
-struct K1Big { const int32_t* list; const int32_t* count; const int32_t* slot; DIntv* slab; const K1Resume* resume; };   // slot[r]: the read's big-slab slot, -1: none; slab: 2 x LH_BIG_INTV per slot (unsorted | sorted); !BIG pass 1: list / count / resume = the reads k_smem_first left, and where
+struct K1Big { const int32_t* list; const int32_t* count; const int32_t* slot; DIntv* slab; union { const K1Resume* resume; int32_t* p2_cnt; }; };   // slot[r]: the read's big-slab slot, -1: none; slab: 2 x LH_BIG_INTV per slot (unsorted | sorted); !BIG pass 1: list / count / resume = the reads k_smem_first left, and where
+// pass 2 over a list, after k_p23_lock: p2_cnt = the reads' count words (pass 3 has run: every interval that gets a slot adds itself), else null (the same word as resume)
 // pass 2's list (k_p2_probe, k_p2_tasks; P2TASK in k_smem_pass): 64-bit entries, the read in the low 27 bits, then the kind.
 //   a call:  xm (8 bits: where bwt_smem1 starts) | min_intv (4) | pbits (LH_BLOOM_K = 19: the probe's answer) | LH_P2E_UNPROBED: the probe did not apply, pbits is 0 and no answer
 //   a share: LH_P2E_SHARE | j << 2 | m - 1 (4 bits): the lane scans the read's intervals and makes every m-th of its calls from the j-th on, probing each itself
@@ -278,6 +279,14 @@ __device__ unsigned long long* lh_k1_lens;
 #define K1_LEN(kind_, v_)
 #endif
 
+// what an interval of s occurrences adds to pass 3's one word of counting: its occurrences, and LH_CNT_REP if they are more than max_occ (a saturating add would do
+// no better: a read whose word reaches LH_CNT_REP is counted again by k_smem_fin).
+// The word cannot carry into LH_CNT_OVF: only an interval that got one of the read's LH_MAX_INTV regular slots is added, at most LH_CNT_REP each — whoever adds
+// (pass 3, or pass 2's calls after it: k_p23_lock)
+#define LH_CNT_REP 0x1000000u
+#define LH_CNT_OVF 0x80000000u
+__device__ __forceinline__ uint32_t dev_cnt_acc(const DOpts& o, u64 s) { return s > (u64)o.max_occ || s >= LH_CNT_REP ? LH_CNT_REP : (uint32_t)s; }
+static_assert((unsigned long long)LH_MAX_INTV * LH_CNT_REP < LH_CNT_OVF, "a read's count word: LH_MAX_INTV adds of at most LH_CNT_REP stay below the overflow bit");
 template <int PASS, bool BIG, int QW = 32>
 __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pass(DIndex ix, DOpts o, int n_reads_all, const uint8_t* __restrict__ seq, const i64* __restrict__ seq_off,
                                                DIntv* __restrict__ intv_out, int32_t* __restrict__ n_intv, int32_t* __restrict__ status, PEnt* __restrict__ slab,
@@ -577,6 +586,12 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             else { todo |= TD_ROW; st = S4_PENDING; }                                                        \
         }                                                                                                    \
     }
+    // pass 2 behind k_p23_lock (big.p2_cnt): pass 3 has counted the read already, so an interval that gets a slot adds its own occurrences to the read's word
+#ifdef LH_P23_NO_P2_COUNT   // test builds only: the add left out (the tests' reads at k_smem_fin's thresholds must then go wrong)
+#define P2_COUNT_ADD()
+#else
+#define P2_COUNT_ADD() { if (big.p2_cnt) atomicAdd(&big.p2_cnt[r], (int)dev_cnt_acc(o, c2)); }
+#endif
     // a backward-sweep interval that cannot be extended and is not contained in the previous MEM becomes a MEM
 #define EMIT_MEM()                                                                                           \
     {                                                                                                        \
@@ -584,7 +599,8 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             DIntv m_; m_.x0 = c0; m_.x1 = c1; m_.x2 = c2; m_.info = (u64)(uint32_t)cinfo | (u64)(i + 1) << 32;  \
             if (P2TASK) {   /* the read's other calls run on other lanes: a slot from the read's counter */     \
                 const int slot_ = atomicAdd(&n_intv[r], 1);                                                  \
-                if (slot_ >= ICAP) ovf = 1; else out[slot_] = m_;                                            \
+                if (slot_ >= ICAP) ovf = 1;                                                                  \
+                else { out[slot_] = m_; P2_COUNT_ADD() }                                                     \
             } else if (on >= ICAP) ovf = 1;                                                                  \
             else { out[on] = m_; on++; K1_REQ(K1T_INTV_W, out + on - 1, 32) }                                \
         }                                                                                                    \
@@ -946,7 +962,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
             if (st == S4_READ_DONE) {
                 rst &= ~P3_NOTEXT;
                 if (ovf) rst |= LH_ST_INTV_OVERFLOW;
-                if (P2TASK) { if (rst) atomicOr(&status[r], rst); }   // (the counter is the calls' own; k_p2_clamp brings it back to the slots there are)
+                if (P2TASK) { if (rst) atomicOr(&status[r], rst); }   // (the counter is the calls' own; k_p2_clamp / k_p2_close brings it back to the slots there are)
                 else { n_intv[r] = on; status[r] = rst; }
                 st = S4_FETCH;
             }
@@ -1118,6 +1134,7 @@ __global__ void __launch_bounds__(64, PASS == 3 ? 8 : LH_SMEM4_WAVES) k_smem_pas
 #undef BWD_ROW_BODY
 #undef BWD_ADVANCE
 #undef EMIT_MEM
+#undef P2_COUNT_ADD
 #undef RF_RUNP
 #undef RF_BT
 #undef RF_C1UNK
@@ -1355,11 +1372,6 @@ __device__ __forceinline__ int dev_seed_count(const DOpts& o, u64 s) {
     u64 c = (s + step - 1) / step;
     return (int)(c < (u64)o.max_occ ? c : (u64)o.max_occ);
 }
-// what an interval of s occurrences adds to pass 3's one word of counting: its occurrences, and LH_CNT_REP if they are more than max_occ (a saturating add would do
-// no better: a read whose word reaches LH_CNT_REP is counted again by k_smem_fin)
-#define LH_CNT_REP 0x1000000u
-#define LH_CNT_OVF 0x80000000u
-__device__ __forceinline__ uint32_t dev_cnt_acc(const DOpts& o, u64 s) { return s > (u64)o.max_occ || s >= LH_CNT_REP ? LH_CNT_REP : (uint32_t)s; }
 // PASS 3 IN LOCKSTEP, one thread per read (new in r03).  bwt_seed_strategy1 is a forward-only loop — no interval lists, no sweeps — so
 // it needs no state machine: every thread walks its own read, the threads of a wave in the same short loop.  Same shortcuts as the
 // pass-3 state machine (k_smem_pass<3>): a walk that starts inside one of the read's unique SMEMs is one PLCP byte (P3TEXT), any other
@@ -1494,6 +1506,276 @@ __global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_
         unsigned t1 = (unsigned)wave_sum_i32((int)n_ext), t2 = (unsigned)wave_sum_i32((int)n_exec), t3 = (unsigned)wave_sum_i32((int)n_kt);
         if (lane == 0 && t1) { atomicAdd(&LH_CTR(ctr)->n_ext, (u64)t1); atomicAdd(&LH_CTR(ctr)->n_ext_exec[2], (u64)t2); atomicAdd(&LH_CTR(ctr)->n_ktree[2], (u64)t3); }
     }
+}
+// PASS 2'S PROBE AND PASS 3 IN ONE LOCKSTEP KERNEL (r15), one thread per read, behind pass 1.  k_p2_probe and k_smem_p3_lock both began with the read's pass-1
+// intervals — the probe four at a time to judge the re-seeding calls, pass 3 one dependent load after the other to find the two longest unique SMEMs and to count
+// the seeds — and pass 3 came after pass 2 only to count pass 2's intervals: its walks use pass 1's unique SMEMs alone (a call of pass 2 has min_intv >= 2: it never
+// emits a unique interval).  mem_collect_intv appends the three passes to one vector that is sorted afterwards, and here K2 ranks a read's intervals by (info, slot)
+// with equal info meaning identical intervals: the order of the slots is free.  So one scan serves both, pass 3 appends right behind pass 1 (slots n1, n1 + 1, ...),
+// and pass 2's calls take their slots behind it from the read's counter, each adding its own occurrences to the read's count word (P2_COUNT_ADD).  The word is left
+// raw in seed_cnt[r] — the LH_CNT_REP sums and LH_CNT_OVF — for k_p2_close, which runs after pass 2 and writes what k_smem_p3_lock writes.
+// The prologue and the probe part are k_p2_probe's, the walk part is k_smem_p3_lock's loop: see there.
+#ifdef LH_P3_KINDS   // development aid (-DLH_P3_KINDS, not shipped; run_front prints and clears it): the batch's intervals per pass and pass 3's walks by kind
+// [0] reads, [1] intervals of pass 1, [2] of pass 3, [3] in the end (k_p2_close); [4] walks decided by text; then per kind k = 0 .. 2 — a table walk that starts
+// inside a third-or-later unique SMEM of pass 1, any other table walk, a final walk that cannot emit (x + min_seed_len >= len) — [5 + k] walks, [8 + k] executed
+// extends, [11 + k] tree reads
+__device__ unsigned long long lh_p3_kinds[16];
+#define P3K_DECL() unsigned k3_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int kk_ = 0; unsigned ke_ = 0, kt_ = 0;
+#define P3K_ADD(i_, v_) k3_[i_] += (unsigned)(v_);
+#define P3K_BEGIN()                                                                                                          \
+    {                                                                                                                        \
+        kk_ = 1; ke_ = n_exec; kt_ = n_kt;                                                                                   \
+        for (int k_ = 0; k_ < (int)n_pass1[r]; ++k_) {                                                                       \
+            const DIntv p_ = out[k_];                                                                                        \
+            const int ps_ = (int)(p_.info >> 32), pe_ = (int)(uint32_t)p_.info;                                              \
+            if (p_.x2 == 1 && !in0 && !in1 && x >= ps_ && x + Lw <= pe_) kk_ = 0;                                            \
+        }                                                                                                                    \
+        if (x + o.min_seed_len >= len) kk_ = 2;                                                                              \
+    }
+#define P3K_END() { k3_[5 + kk_] += 1; k3_[8 + kk_] += n_exec - ke_; k3_[11 + kk_] += n_kt - kt_; }
+#define P3K_FLUSH()                                                                                                          \
+    for (int i_ = 0; i_ < 14; ++i_) { const unsigned t_ = (unsigned)wave_sum_i32((int)k3_[i_]); if (lane == 0 && t_) atomicAdd(&lh_p3_kinds[i_], (unsigned long long)t_); }
+#else
+#define P3K_DECL()
+#define P3K_ADD(i_, v_)
+#define P3K_BEGIN()
+#define P3K_END()
+#define P3K_FLUSH()
+#endif
+__global__ void __launch_bounds__(256, 6) k_p23_lock(DIndex ix, DOpts o, int n_reads, const uint8_t* __restrict__ seq, const uint32_t* __restrict__ q4, const i64* __restrict__ seq_off,
+                                                   DIntv* __restrict__ intv_out, int32_t* __restrict__ n_intv, DCounters* __restrict__ ctr, int32_t* __restrict__ seed_cnt,
+                                                   u64* __restrict__ tasks, int32_t* __restrict__ n_tasks, int32_t* __restrict__ n_pass1, P2Calls* __restrict__ calls) {
+    __shared__ u64 ent[LH_P2_SPLIT * 256];   // entry j of thread t at ent[j * 256 + t]
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
+    const bool probe = ix.bloom1 != nullptr && ix.rep_t != nullptr && o.min_seed_len >= LH_BLOOM_K;
+    const int split_len = (int)(o.min_seed_len * o.split_factor + .499);
+#ifdef LH_P2_PROBE_WEAK
+    const u64 pmask = (1ull << (LH_BLOOM_K - 1)) - 1;
+#else
+    const u64 pmask = (1ull << LH_BLOOM_K) - 1;
+#endif
+    const int Lw = o.min_seed_len + 1;
+    const bool text_ok = ix.isa != nullptr && ix.plcp != nullptr && o.max_mem_intv > 1;
+    int m = 0, n_drop = 0, n_prob = 0, n_unpr = 0, share = 0;
+    // what the walk part needs of the scan: the read, its length (0: not walked), its intervals so far, the two longest unique SMEMs [us, ue) packed a byte each
+    // (us0 | ue0 << 8 | us1 << 16 | ue1 << 24: k_smem_pass's uspan) with their text positions, and the count word
+    i64 off = 0;
+    int len = 0, on = 0;
+    uint32_t uspan = 0, cnt = 0;
+    u64 up0 = 0, up1 = 0;
+    if (r < n_reads) {
+        off = seq_off[r];
+        len = (int)(seq_off[r + 1] - off);
+        if (len > LH_MAXLEN || len < o.min_seed_len || o.max_mem_intv <= 0) len = 0;
+        on = n_intv[r] < LH_MAX_INTV ? n_intv[r] : LH_MAX_INTV;
+        n_pass1[r] = on;
+        const bool pick = text_ok && len > 0;
+        const uint4* const iv = (const uint4*)(intv_out + (size_t)r * LH_MAX_INTV);   // an interval: (x0, x1), (x2, info)
+        for (int k0 = 0; k0 < on; k0 += 4) {   // four intervals at a time: each step's loads are in flight together
+            uint2 lo[4];   // (x0 alone: neither part looks at x1)
+            uint4 hi[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                lo[q] = uint2{0, 0}; hi[q] = uint4{0, 0, 0, 0};
+                if (k0 + q < on) { lo[q] = *(const uint2*)&iv[2 * (k0 + q)]; hi[q] = iv[2 * (k0 + q) + 1]; }
+            }
+            // pass 3's choice in its order and with its tie rule (strict >: the first of equals wins), and the running count
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (k0 + q >= on) continue;
+                const int ps = (int)hi[q].w, pe = (int)hi[q].z;
+                const u64 x0 = (u64)lo[q].x | (u64)lo[q].y << 32, x2 = (u64)hi[q].x | (u64)hi[q].y << 32;
+                cnt += dev_cnt_acc(o, x2);
+                if (!pick || x2 != 1 || pe - ps < Lw) continue;
+                const int l0 = (int)((uspan >> 8) & 0xff) - (int)(uspan & 0xff), l1 = (int)(uspan >> 24) - (int)((uspan >> 16) & 0xff);
+                const uint32_t sp = (uint32_t)ps | (uint32_t)pe << 8;
+                if (pe - ps > l0) { uspan = uspan << 16 | sp; up1 = up0; up0 = x0; }
+                else if (pe - ps > l1) { uspan = (uspan & 0xffffu) | sp << 16; up1 = x0; }
+            }
+            // the two SMEMs' suffix-array reads beside the probe's own: after the last four intervals the choice is made (a row is one read; a position needs none)
+            const bool last = k0 + 4 >= on;
+            u64 s0 = up0 & ~LH_POSF, s1 = up1 & ~LH_POSF;
+            const bool rd0 = last && (uspan & 0xffffu) && !(up0 & LH_POSF), rd1 = last && (uspan >> 16) && !(up1 & LH_POSF);
+            if (rd0) s0 = ix.sa[up0];
+            if (rd1) s1 = ix.sa[up1];
+            bool call[4], in[4];
+            int xm[4], w0[4];
+            uint32_t base[4];
+            u64 pos[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int s = (int)hi[q].w, e = (int)hi[q].z;
+                const u64 x0 = (u64)lo[q].x | (u64)lo[q].y << 32, x2 = (u64)hi[q].x | (u64)hi[q].y << 32;
+                call[q] = k0 + q < on && e - s >= split_len && x2 <= (u64)o.split_width;   // long and rare
+                xm[q] = (s + e) >> 1; w0[q] = xm[q] - (LH_BLOOM_K - 1) - s;
+                in[q] = call[q] && probe && w0[q] >= 0 && xm[q] + LH_BLOOM_K <= e;   // the windows lie inside the SMEM
+                base[q] = 4; pos[q] = x0 & ~LH_POSF;
+                if (call[q]) base[q] = seq[off + xm[q]];
+                if (in[q] && !(x0 & LH_POSF)) pos[q] = ix.sa[x0];   // stored as rows: the first row's occurrence
+            }
+            u64 b0[4], b1[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                call[q] = call[q] && base[q] <= 3;   // bwt_smem1a returns at once on an ambiguous base: no call
+                in[q] = in[q] && call[q];
+                b0[q] = b1[q] = 0; pos[q] += (u64)w0[q];   // the first window's text position
+                if (in[q]) { b0[q] = ix.rep_t[pos[q] >> 6]; b1[q] = ix.rep_t[(pos[q] >> 6) + 1]; }
+            }
+            if (last) { up0 = s0; up1 = s1; }   // from here on: text positions
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (!call[q]) continue;
+                const uint32_t sh = (uint32_t)(pos[q] & 63);
+                const u64 pbits = (sh ? (b0[q] >> sh) | (b1[q] << (64 - sh)) : b0[q]) & pmask;
+                if (in[q] && !pbits) { ++n_drop; continue; }
+                if (in[q]) ++n_prob; else ++n_unpr;
+                const u64 min_intv = ((u64)hi[q].x | (u64)hi[q].y << 32) + 1;
+                if (m < LH_P2_SPLIT)
+                    ent[m * 256 + threadIdx.x] = (u64)(uint32_t)r | (u64)xm[q] << LH_P2E_XM | min_intv << LH_P2E_MIN | (in[q] ? pbits << LH_P2E_PBITS : LH_P2E_UNPROBED);
+                ++m;
+            }
+        }
+        if (m > LH_P2_SPLIT) { share = 1; m = LH_P2_SPLIT; n_prob = n_unpr = 0; }   // (a share's lane judges its calls again: only the dropped ones count here)
+    }
+    {   // the list and the listers' counts, as k_p2_probe
+        const int incl = wave_scan_add_i32(m);
+        const int tot = wave_readlane(incl, 63);
+        int basep = 0;
+        if (lane == 0 && tot) basep = atomicAdd(n_tasks, tot);
+        basep = wave_readlane(basep, 0);
+        for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = share ? p2_share_entry(r, j, m) : ent[j * 256 + threadIdx.x];
+        const int t_drop = wave_sum_i32(n_drop), t_prob = wave_sum_i32(n_prob), t_unpr = wave_sum_i32(n_unpr), t_sh = __popcll(__ballot(share));
+        if (lane == 0) {
+            if (t_drop) atomicAdd(&LH_CTR(calls)->dropped, (u64)t_drop);
+            if (t_prob) atomicAdd(&LH_CTR(calls)->probed, (u64)t_prob);
+            if (t_unpr) atomicAdd(&LH_CTR(calls)->unprobed, (u64)t_unpr);
+            if (t_sh) atomicAdd(&LH_CTR(calls)->shares, (u64)t_sh);
+        }
+    }
+    // ---- pass 3: k_smem_p3_lock's walks, appended behind pass 1's intervals ----
+    const PEnt* const kt = (const PEnt*)ix.ktree;
+    const int ktl = kt ? ix.ktree_levels : 0;
+    unsigned n_ext = 0, n_exec = 0, n_kt = 0;
+    P3K_DECL()
+    if (r < n_reads) {
+        DIntv* out = intv_out + (size_t)r * LH_MAX_INTV;
+#define QN(i_) ((int)(dev_nib8(q4, off + (i_)) & 0xf))
+#define P23_US0 ((int)(uspan & 0xff))
+#define P23_UE0 ((int)((uspan >> 8) & 0xff))
+#define P23_US1 ((int)((uspan >> 16) & 0xff))
+#define P23_UE1 ((int)(uspan >> 24))
+        int x = 0, notext = 0;
+        P3K_ADD(0, 1) P3K_ADD(1, on)
+        while (x < len) {
+            if (QN(x) > 3) { ++x; continue; }
+            const int in0 = x >= P23_US0 && x + Lw <= P23_UE0, in1 = x >= P23_US1 && x + Lw <= P23_UE1;
+            if (text_ok && !notext && (in0 || in1)) {   // by text: unique iff the suffix there shares fewer than Lw bases with every other one
+                const i64 tp = in0 ? (i64)up0 + (x - P23_US0) : (i64)up1 + (x - P23_US1);
+                if ((int)ix.plcp[tp] < Lw) {
+                    if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
+                    else {
+                        DIntv mm; mm.x0 = LH_POSF | (u64)tp; mm.x1 = 0; mm.x2 = 1; mm.info = (u64)x << 32 | (u64)(x + Lw); out[on++] = mm;
+                        cnt += dev_cnt_acc(o, 1);
+                    }
+                    n_ext += (unsigned)(Lw - 1);
+                    x += Lw;
+                    P3K_ADD(4, 1)
+                    continue;
+                }
+                notext = 1;   // it occurs again: the walk as written, from x
+            }
+            notext = 0;
+            // bwt_seed_strategy1 from x
+            P3K_BEGIN()
+            DIntv c = dev_set_intv(ix, QN(x));
+            int i = x + 1;
+            uint32_t fcode = (uint32_t)QN(x);
+            if (ktl > 1 && x + ktl <= len && o.min_seed_len >= ktl) {   // the walk's first ktl bases from the tree's deepest level (none of those steps can end it)
+                uint32_t w0 = dev_nib8(q4, off + x), w1 = dev_nib8(q4, off + x + 8);
+                uint32_t m0 = w0, m1 = w1;
+                if (ktl < 8) { m0 &= (1u << (4 * ktl)) - 1u; m1 = 0; }
+                else if (ktl < 16) m1 &= (1u << (4 * (ktl - 8))) - 1u;
+                if (!((m0 | m1) & 0x44444444u)) {
+                    uint32_t ca = w0 & 0x33333333u, cb = w1 & 0x33333333u;
+                    ca = (ca | ca >> 2) & 0x0f0f0f0fu; ca = (ca | ca >> 4) & 0x00ff00ffu; ca = (ca | ca >> 8) & 0xffffu;
+                    cb = (cb | cb >> 2) & 0x0f0f0f0fu; cb = (cb | cb >> 4) & 0x00ff00ffu; cb = (cb | cb >> 8) & 0xffffu;
+                    const uint32_t code = (ca | cb << 16) & (ktl >= 16 ? 0xffffffffu : (1u << (2 * ktl)) - 1u);
+                    const PEnt te = kt[(((1ull << (2 * ktl)) - 4) / 3) + code];
+                    c.x0 = PE_X0(te); c.x1 = PE_X1(te); c.x2 = PE_X2(te);
+                    n_ext += (unsigned)(ktl - 1);
+                    i = x + ktl;
+                }
+            }
+            int nx = len;   // where the next walk starts
+            for (; i < len; ++i) {
+                const int b = QN(i);
+                if (b > 3) { nx = i + 1; break; }
+                DIntv ok;
+                const int lnew = i + 1 - x;
+                if (lnew <= ktl) {   // a short match: its interval is the tree's entry
+                    fcode |= (uint32_t)b << (2 * (lnew - 1));
+                    const PEnt te = kt[(((1ull << (2 * lnew)) - 4) / 3) + fcode];
+                    ok.x0 = PE_X0(te); ok.x1 = PE_X1(te); ok.x2 = PE_X2(te); ok.info = 0;
+                    ++n_kt;
+                } else { ok = dev_extend_c(ix, c, 3 - b, 0); ++n_exec; }
+                ++n_ext;
+                if (ok.x2 < (u64)o.max_mem_intv && i - x >= o.min_seed_len) {
+                    if (ok.x2 > 0) {
+                        if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
+                        else {
+                            ok.info = (u64)x << 32 | (u64)(i + 1); out[on++] = ok;
+                            cnt += dev_cnt_acc(o, ok.x2);
+                        }
+                    }
+                    nx = i + 1;
+                    break;
+                }
+                c = ok;
+            }
+            x = nx;
+            P3K_END()
+        }
+#undef QN
+#undef P23_US0
+#undef P23_UE0
+#undef P23_US1
+#undef P23_UE1
+        P3K_ADD(2, on - n_pass1[r])
+        n_intv[r] = on;             // pass 2's calls go on from here
+        seed_cnt[r] = (int)cnt;     // raw: k_p2_close finishes it
+    }
+    P3K_FLUSH()
+    if (ctr) {
+        unsigned t1 = (unsigned)wave_sum_i32((int)n_ext), t2 = (unsigned)wave_sum_i32((int)n_exec), t3 = (unsigned)wave_sum_i32((int)n_kt);
+        if (lane == 0 && t1) { atomicAdd(&LH_CTR(ctr)->n_ext, (u64)t1); atomicAdd(&LH_CTR(ctr)->n_ext_exec[2], (u64)t2); atomicAdd(&LH_CTR(ctr)->n_ktree[2], (u64)t3); }
+    }
+}
+// behind pass 2 over a list that followed k_p23_lock: what k_p2_clamp does (a read whose calls asked for more slots than it has: flagged by the call that was refused),
+// and the end of k_smem_p3_lock — the read's count word (pass 3's sums and those pass 2's calls added) becomes its seed count, l_rep 0; the reads with more than 16
+// intervals or one above max_occ are listed for k_smem_fin, which overwrites both words.  One thread per read, one append per wave.
+__global__ void __launch_bounds__(256) k_p2_close(int n_reads, int32_t* __restrict__ n_intv, int32_t* __restrict__ status, int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep,
+                                                   int32_t* __restrict__ fin_list, int32_t* __restrict__ fin_count) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
+    int fin = 0;
+    if (r < n_reads) {
+        int on = n_intv[r];
+        if (on > LH_MAX_INTV) n_intv[r] = on = LH_MAX_INTV;
+        const uint32_t cnt = (uint32_t)seed_cnt[r];
+        if (cnt & LH_CNT_OVF) status[r] |= LH_ST_INTV_OVERFLOW;
+        seed_cnt[r] = (int)(cnt & (LH_CNT_REP - 1)); l_rep[r] = 0;
+        fin = on > 16 || (cnt & ~LH_CNT_OVF) >= LH_CNT_REP;
+#ifdef LH_P3_KINDS
+        atomicAdd(&lh_p3_kinds[3], (unsigned long long)on);
+#endif
+    }
+#ifdef LH_P23_NO_FIN_LIST   // test builds only: no read listed (the tests' reads of 17 intervals must then reach K2 unsorted)
+    fin = 0;
+#endif
+    const u64 m = __ballot(fin);
+    int base = 0;
+    if (lane == 0 && m) base = atomicAdd(fin_count, __popcll(m));
+    base = wave_readlane(base, 0);
+    if (fin) fin_list[base + lanes_below(m, lane)] = r;
 }
 
 // sort each read's intervals by info (rank sort; equal keys are identical intervals), seed counts, l_rep.  16 lanes per read

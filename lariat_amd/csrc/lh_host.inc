@@ -562,7 +562,6 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
 #ifdef LH_K1_TRACE
         { int rc = k1_trace_replay(c, trace, N, g4); if (rc) return rc; }
 #endif
-        T_BEGIN("k_smem4_p2");
         // Pass 2 runs over a list (k_smem4.h: P2TASK).  By default k_p2_probe makes it: every re-seeding call judged in lockstep, the calls that can contribute listed one
         // by one with the probe's answer, a read with more than LH_P2_SPLIT of them as shares.  LH_F_P2_TASKS: every read with a call as shares, up to LH_P2_SPLIT lanes
         // scanning and probing a read's calls themselves (k_p2_tasks; pass 2 45 -> 31 ms on the repeat input, but 4.7 -> 5.4 ms on unique sequence).  LH_F_P2_SCAN: the
@@ -575,34 +574,65 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         p2_probe = false;   // (the trace build's list-length histograms are the state machine's)
 #endif
         const bool p2_tasks = p2_list_ok && !p2_probe && ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek->prev_wave_reads >= ext_long_min(N)));
-        K1Big p2 = nobig;
-        if (p2_probe || p2_tasks) { p2.list = (const int32_t*)c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo; }   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
-        if (p2_probe)
-            LH_LAUNCH(k_p2_probe, (N + 255) / 256, 256, c->stream, ix4, o, N, (const uint8_t*)c->b.seq, (const i64*)c->b.seq_off, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks,
-                      &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
-        else if (p2_tasks)
-            LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
-        if (qw_small) smem_pass<2, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, p2);
-        else smem_pass<2, false>(c, ix4, o, N, g4, p2);
-        if (p2_probe || p2_tasks) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
-        T_END();
-#ifdef LH_K1_TRACE
-        { int rc = k1_trace_lens(c, trace); if (rc) return rc; }
-#endif
-        T_BEGIN("k_smem4_p3");
         // pass 3 in lockstep is the last to touch a read's regular slots and walks them anyway: it counts the read's seeds and lists the few reads that need their
         // intervals sorted in memory (k_smem_fin below); K2 ranks the others' inside its groups.  Every other path — no pass 3, the state machine's, the lane-per-seed
         // K2, the trace build — keeps k_smem_fin over all reads
-        bool p3_counts = o.max_mem_intv > 0 && q4 && !(c->flags & LH_F_SEED_LANE);
+        const bool p3_lock = o.max_mem_intv > 0 && q4;   // forward-only walks: one thread per read, in lockstep
+        bool p3_counts = p3_lock && !(c->flags & LH_F_SEED_LANE);
 #ifdef LH_K1_TRACE
         p3_counts = false;
 #endif
-        if (o.max_mem_intv > 0 && q4)   // forward-only walks: one thread per read, in lockstep
-            LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr,
-                      p3_counts ? c->d_seed_cnt : nullptr, p3_counts ? c->d_l_rep : nullptr, p3_counts ? c->d_fin_list : nullptr, p3_counts ? &c->d_next_read->n_fin : nullptr);
-        else if (o.max_mem_intv > 0)
-            smem_pass<3, false>(c, ix4, o, N, g3, nobig);
-        T_END();
+        // The default, where the probe kernel and the counting pass 3 both run: ONE lockstep kernel behind pass 1 does the probe's work and pass 3's (k_p23_lock: one scan
+        // of the pass-1 intervals serves both; pass 3's walks need nothing of pass 2), pass 2 then appends behind pass 3's intervals and adds its own counts, and
+        // k_p2_close ends it.  The bracket "k_smem4_p3" then comes FIRST and holds k_p23_lock — the probe's time with it — and "k_smem4_p2" holds pass 2 and k_p2_close.
+        // LH_F_P3_LAST keeps the sequence below: probe, pass 2, clamp, pass 3.
+        const bool p23 = p2_probe && p3_counts && !(c->flags & LH_F_P3_LAST);
+        K1Big p2 = nobig;
+        if (p2_probe || p2_tasks) { p2.list = (const int32_t*)c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo; }   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
+        if (p23) {
+            T_BEGIN("k_smem4_p3");
+            LH_LAUNCH(k_p23_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, (const uint8_t*)c->b.seq, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_ctr, c->d_seed_cnt, c->d_p2_tasks,
+                      &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
+            T_END();
+            T_BEGIN("k_smem4_p2");
+            p2.p2_cnt = c->d_seed_cnt;
+            if (qw_small) smem_pass<2, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, p2);
+            else smem_pass<2, false>(c, ix4, o, N, g4, p2);
+            LH_LAUNCH(k_p2_close, (N + 255) / 256, 256, c->stream, N, c->d_n_intv, c->d_status, c->d_seed_cnt, c->d_l_rep, c->d_fin_list, &c->d_next_read->n_fin);
+            T_END();
+#ifdef LH_P3_KINDS   // a development build's read-out (it waits for the stream): k_smem4.h, lh_p3_kinds
+            {
+                unsigned long long k[16], zero[16] = {0};
+                HIPCHK(hipStreamSynchronize(c->stream));
+                HIPCHK(hipMemcpyFromSymbol(k, HIP_SYMBOL(lh_p3_kinds), sizeof k));
+                HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(lh_p3_kinds), zero, sizeof zero));
+                fprintf(stderr, "[lh] p3_kinds:");
+                for (int i = 0; i < 14; ++i) fprintf(stderr, " %llu", k[i]);
+                fprintf(stderr, "\n");
+            }
+#endif
+        } else {
+            T_BEGIN("k_smem4_p2");
+            if (p2_probe)
+                LH_LAUNCH(k_p2_probe, (N + 255) / 256, 256, c->stream, ix4, o, N, (const uint8_t*)c->b.seq, (const i64*)c->b.seq_off, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks,
+                          &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
+            else if (p2_tasks)
+                LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
+            if (qw_small) smem_pass<2, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, p2);
+            else smem_pass<2, false>(c, ix4, o, N, g4, p2);
+            if (p2_probe || p2_tasks) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
+            T_END();
+#ifdef LH_K1_TRACE
+            { int rc = k1_trace_lens(c, trace); if (rc) return rc; }
+#endif
+            T_BEGIN("k_smem4_p3");
+            if (p3_lock)
+                LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr,
+                          p3_counts ? c->d_seed_cnt : nullptr, p3_counts ? c->d_l_rep : nullptr, p3_counts ? c->d_fin_list : nullptr, p3_counts ? &c->d_next_read->n_fin : nullptr);
+            else if (o.max_mem_intv > 0)
+                smem_pass<3, false>(c, ix4, o, N, g3, nobig);
+            T_END();
+        }
         T_BEGIN("k_smem_fin");
         // reads whose intervals outgrew their LH_MAX_INTV slots: the three passes again into the big slab (BWA's vectors grow: no read is refused)
         { int rc = k1_big_round(c, o, ix4, N, 0); if (rc) return rc; }
@@ -881,7 +911,7 @@ static int pipe_align(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
     if (!c->resident) return set_err(LH_E_ARG, "no batch resident: call lh_batch_upload first");
     if (opts->abi_version != LH_ABI_VERSION) return set_err(LH_E_ARG, "lh_opts.abi_version does not match LH_ABI_VERSION (use lh_opts_init)");
-    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES | LH_F_RFA_SLAB | LH_F_P2_SCAN)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
+    if (opts->flags & ~(LH_F_NO_SWEEP_FILTER | LH_F_EXT_WAVE | LH_F_EXT_SERIAL | LH_F_CHAIN_WAVE | LH_F_P2_TASKS | LH_F_RESCUE_FULL | LH_F_SEED_LANE | LH_F_TAIL_PASSES | LH_F_RFA_SLAB | LH_F_P2_SCAN | LH_F_P3_LAST)) return set_err(LH_E_ARG, "lh_opts.flags: unknown bit set");
     HIPCHK(hipSetDevice(c->idx->device));
     {
         std::vector<void*> fl;

@@ -183,6 +183,20 @@ int lh_last_p2_calls(lh_context* c, int64_t* out) {
     return LH_OK;
 }
 
+// the reads the first pipeline's last K1 listed for k_smem_fin (the list lives until the pipeline's next K1)
+int lh_last_fin_list(lh_context* c, int32_t* out, int64_t cap, int64_t* n) {
+    if (!c || !n || cap < 0 || (cap && !out)) return set_err(LH_E_ARG, "lh_last_fin_list: null argument");
+    if (!c->d_fin_list || !c->d_next_read) return set_err(LH_E_ARG, "lh_last_fin_list: call lh_align_resident or lh_stage_dump_resident first");
+    HIPCHK(hipSetDevice(c->idx->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int32_t n_fin = 0;
+    HIPCHK(hipMemcpy(&n_fin, &c->d_next_read->n_fin, sizeof n_fin, hipMemcpyDeviceToHost));
+    *n = n_fin;
+    const int64_t k = n_fin < cap ? n_fin : cap;
+    if (k > 0) HIPCHK(hipMemcpy(out, c->d_fin_list, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LH_OK;
+}
+
 // part behind acc (the first part becomes acc): merged into a new result, and both are freed whatever the outcome.  The rounds' parts and the lanes' fold this way
 static int merge_into(lh_result*& acc, lh_result* part) {
     if (!acc) { acc = part; return LH_OK; }
