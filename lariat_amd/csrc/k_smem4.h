@@ -1250,89 +1250,121 @@ __global__ void __launch_bounds__(256) k_p2_tasks(DOpts o, int n_reads, const DI
     basep = wave_readlane(basep, 0);
     for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = p2_share_entry(r, j, m);
 }
-// PASS 2'S PROBE IN LOCKSTEP (r14), one thread per read.  What S4_P2_NEXT and the probe states do before a re-seeding call starts is the same short program for every
-// read — the read's pass-1 intervals, the middle base, one text position, two words of rep_t — and in unique sequence it ends most calls before they begin (the probe
-// finds no repeated k-mer: the call cannot contribute).  The state machine paid a staged query and four dependent turns for each of them.  Here the program runs in
-// plain loops, a read's loads issued together, and only what survives is listed: a call with the probe's answer in its entry (or marked unprobed where the probe does
-// not apply: windows not inside the SMEM, no filter, no rep_t), which pass 2 starts without reading an interval.  A read with more than LH_P2_SPLIT surviving calls
-// is listed as LH_P2_SPLIT share entries instead (k_p2_tasks' form: the list stays within its LH_P2_SPLIT x n_reads slots, and a repeat-rich read's calls still
-// spread over lanes).  The tests are S4_P2_NEXT's, in its order; the entries of a block's reads are appended with one atomicAdd per wave.
+// THE LOCKSTEP LISTERS' JUDGE (k_p2_probe, k_p23_lock), a thread's state over its read.  What S4_P2_NEXT and the probe states do before a re-seeding call starts is the
+// same short program for every read — the read's pass-1 intervals, the middle base, one text position, two words of rep_t — and in unique sequence it ends most calls
+// before they begin (the probe finds no repeated k-mer: the call cannot contribute).  Here it runs on four intervals at a time, each stage's loads in flight together;
+// the stages are separate so that a kernel can issue loads of its own between them.  The tests are S4_P2_NEXT's, in its order.  What survives gets an entry: a call
+// with the probe's answer (or marked unprobed where the probe does not apply: windows not inside the SMEM, no filter, no rep_t), which pass 2 starts without reading
+// an interval.
+struct P2Judge {
+    bool probe;
+    int split_len;
+    int share = 0;   // the read is listed as shares (close)
+    int m = 0, n_drop = 0, n_prob = 0, n_unpr = 0;   // the read's surviving calls (the first LH_P2_SPLIT of them in ent[]) and its share of the P2Calls counts
+    uint2 lo[4];   // an interval is (x0, x1), (x2, info); of the first half x0 alone: nothing here looks at x1
+    uint4 hi[4];
+    bool call[4], in[4];
+    int xm[4], w0[4];
+    uint32_t base[4];
+    u64 pos[4], b0[4], b1[4];
+    __device__ __forceinline__ P2Judge(const DIndex& ix, const DOpts& o)
+        : probe(ix.bloom1 != nullptr && ix.rep_t != nullptr && o.min_seed_len >= LH_BLOOM_K),   // (k_smem_pass: filt && ix.rep_t)
+          split_len((int)(o.min_seed_len * o.split_factor + .499)) {}
+    __device__ __forceinline__ u64 x0(int q) const { return (u64)lo[q].x | (u64)lo[q].y << 32; }
+    __device__ __forceinline__ u64 x2(int q) const { return (u64)hi[q].x | (u64)hi[q].y << 32; }
+    __device__ __forceinline__ void load(const uint4* iv, int k0, int on) {   // intervals k0 .. k0 + 3 of the read's `on`
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            lo[q] = uint2{0, 0}; hi[q] = uint4{0, 0, 0, 0};
+            if (k0 + q < on) { lo[q] = *(const uint2*)&iv[2 * (k0 + q)]; hi[q] = iv[2 * (k0 + q) + 1]; }
+        }
+    }
+    // stage 1: which of the four is a call, and its middle base and text position on their way
+    __device__ __forceinline__ void classify(const DIndex& ix, const DOpts& o, const uint8_t* __restrict__ seq, i64 off, int k0, int on) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int s = (int)hi[q].w, e = (int)hi[q].z;
+            call[q] = k0 + q < on && e - s >= split_len && x2(q) <= (u64)o.split_width;   // long and rare
+            xm[q] = (s + e) >> 1; w0[q] = xm[q] - (LH_BLOOM_K - 1) - s;
+            in[q] = call[q] && probe && w0[q] >= 0 && xm[q] + LH_BLOOM_K <= e;   // the windows lie inside the SMEM
+            base[q] = 4; pos[q] = x0(q) & ~LH_POSF;
+            if (call[q]) base[q] = seq[off + xm[q]];
+            if (in[q] && !(x0(q) & LH_POSF)) pos[q] = ix.sa[x0(q)];   // stored as rows: the first row's occurrence
+        }
+    }
+    // stage 2: the two words of rep_t that hold the windows' bits
+    __device__ __forceinline__ void fetch_bits(const DIndex& ix) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            call[q] = call[q] && base[q] <= 3;   // bwt_smem1a returns at once on an ambiguous base: no call
+            in[q] = in[q] && call[q];
+            b0[q] = b1[q] = 0; pos[q] += (u64)w0[q];   // the first window's text position
+            if (in[q]) { b0[q] = ix.rep_t[pos[q] >> 6]; b1[q] = ix.rep_t[(pos[q] >> 6) + 1]; }
+        }
+    }
+    // stage 3: the probe's answer; a surviving call's entry (entry j of thread t at ent[j * 256 + t])
+    __device__ __forceinline__ void settle(int r, u64* ent) {
+#ifdef LH_P2_PROBE_WEAK   // test builds only: a probe that overlooks the last window (the tests' planted k-mer there must then go missing)
+        const u64 pmask = (1ull << (LH_BLOOM_K - 1)) - 1;
+#else
+        const u64 pmask = (1ull << LH_BLOOM_K) - 1;
+#endif
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!call[q]) continue;
+            const uint32_t sh = (uint32_t)(pos[q] & 63);
+            const u64 pbits = (sh ? (b0[q] >> sh) | (b1[q] << (64 - sh)) : b0[q]) & pmask;
+            if (in[q] && !pbits) { ++n_drop; continue; }
+            if (in[q]) ++n_prob; else ++n_unpr;
+            const u64 min_intv = x2(q) + 1;
+            if (m < LH_P2_SPLIT)
+                ent[m * 256 + threadIdx.x] = (u64)(uint32_t)r | (u64)xm[q] << LH_P2E_XM | min_intv << LH_P2E_MIN | (in[q] ? pbits << LH_P2E_PBITS : LH_P2E_UNPROBED);
+            ++m;
+        }
+    }
+    // after the read's last four: a read with more than LH_P2_SPLIT surviving calls is listed as LH_P2_SPLIT share entries instead (k_p2_tasks' form: the list stays
+    // within its LH_P2_SPLIT x n_reads slots, and a repeat-rich read's calls still spread over lanes).  A share's lane judges its calls again: only the dropped ones
+    // count here
+    __device__ __forceinline__ void close() { if (m > LH_P2_SPLIT) { share = 1; m = LH_P2_SPLIT; n_prob = n_unpr = 0; } }
+    // the list and the listers' counts, by every thread of the block (r past the batch: m = 0).  The entries of a wave's reads are appended with one atomicAdd.
+    __device__ __forceinline__ void flush(int r, int lane, const u64* ent, u64* __restrict__ tasks, int32_t* __restrict__ n_tasks, P2Calls* __restrict__ calls) {
+        const int incl = wave_scan_add_i32(m);
+        const int tot = wave_readlane(incl, 63);
+        int basep = 0;
+        if (lane == 0 && tot) basep = atomicAdd(n_tasks, tot);
+        basep = wave_readlane(basep, 0);
+        for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = share ? p2_share_entry(r, j, m) : ent[j * 256 + threadIdx.x];
+        const int t_drop = wave_sum_i32(n_drop), t_prob = wave_sum_i32(n_prob), t_unpr = wave_sum_i32(n_unpr), t_sh = __popcll(__ballot(share));
+        if (lane == 0) {
+            if (t_drop) atomicAdd(&LH_CTR(calls)->dropped, (u64)t_drop);
+            if (t_prob) atomicAdd(&LH_CTR(calls)->probed, (u64)t_prob);
+            if (t_unpr) atomicAdd(&LH_CTR(calls)->unprobed, (u64)t_unpr);
+            if (t_sh) atomicAdd(&LH_CTR(calls)->shares, (u64)t_sh);
+        }
+    }
+};
+// PASS 2'S PROBE IN LOCKSTEP (r14), one thread per read: the judge over the read's pass-1 intervals, and its list.  The state machine paid a staged query and four
+// dependent turns for each call that the probe ends; here only what survives is listed.
 __global__ void __launch_bounds__(256) k_p2_probe(DIndex ix, DOpts o, int n_reads, const uint8_t* __restrict__ seq, const i64* __restrict__ seq_off, const DIntv* __restrict__ intv,
                                                    const int32_t* __restrict__ n_intv, u64* __restrict__ tasks, int32_t* __restrict__ n_tasks, int32_t* __restrict__ n_pass1,
                                                    P2Calls* __restrict__ calls) {
-    __shared__ u64 ent[LH_P2_SPLIT * 256];   // entry j of thread t at ent[j * 256 + t]
+    __shared__ u64 ent[LH_P2_SPLIT * 256];
     const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
-    const bool probe = ix.bloom1 != nullptr && ix.rep_t != nullptr && o.min_seed_len >= LH_BLOOM_K;   // (k_smem_pass: filt && ix.rep_t)
-    const int split_len = (int)(o.min_seed_len * o.split_factor + .499);
-#ifdef LH_P2_PROBE_WEAK   // test builds only: a probe that overlooks the last window (the tests' planted k-mer there must then go missing)
-    const u64 pmask = (1ull << (LH_BLOOM_K - 1)) - 1;
-#else
-    const u64 pmask = (1ull << LH_BLOOM_K) - 1;
-#endif
-    int m = 0, n_drop = 0, n_prob = 0, n_unpr = 0, share = 0;
+    P2Judge j(ix, o);
     if (r < n_reads) {
         const int on = n_intv[r] < LH_MAX_INTV ? n_intv[r] : LH_MAX_INTV;
         n_pass1[r] = on;
-        const uint4* const iv = (const uint4*)(intv + (size_t)r * LH_MAX_INTV);   // an interval: (x0, x1), (x2, info)
+        const uint4* const iv = (const uint4*)(intv + (size_t)r * LH_MAX_INTV);
         const i64 off = seq_off[r];
-        for (int k0 = 0; k0 < on; k0 += 4) {   // four intervals at a time: each step's loads are in flight together
-            uint4 lo[4], hi[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                lo[q] = hi[q] = uint4{0, 0, 0, 0};
-                if (k0 + q < on) { lo[q] = iv[2 * (k0 + q)]; hi[q] = iv[2 * (k0 + q) + 1]; }
-            }
-            bool call[4], in[4];
-            int xm[4], w0[4];
-            uint32_t base[4];
-            u64 pos[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int s = (int)hi[q].w, e = (int)hi[q].z;
-                const u64 x0 = (u64)lo[q].x | (u64)lo[q].y << 32, x2 = (u64)hi[q].x | (u64)hi[q].y << 32;
-                call[q] = k0 + q < on && e - s >= split_len && x2 <= (u64)o.split_width;   // long and rare
-                xm[q] = (s + e) >> 1; w0[q] = xm[q] - (LH_BLOOM_K - 1) - s;
-                in[q] = call[q] && probe && w0[q] >= 0 && xm[q] + LH_BLOOM_K <= e;   // the windows lie inside the SMEM
-                base[q] = 4; pos[q] = x0 & ~LH_POSF;
-                if (call[q]) base[q] = seq[off + xm[q]];
-                if (in[q] && !(x0 & LH_POSF)) pos[q] = ix.sa[x0];   // stored as rows: the first row's occurrence
-            }
-            u64 b0[4], b1[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                call[q] = call[q] && base[q] <= 3;   // bwt_smem1a returns at once on an ambiguous base: no call
-                in[q] = in[q] && call[q];
-                b0[q] = b1[q] = 0; pos[q] += (u64)w0[q];   // the first window's text position
-                if (in[q]) { b0[q] = ix.rep_t[pos[q] >> 6]; b1[q] = ix.rep_t[(pos[q] >> 6) + 1]; }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (!call[q]) continue;
-                const uint32_t sh = (uint32_t)(pos[q] & 63);
-                const u64 pbits = (sh ? (b0[q] >> sh) | (b1[q] << (64 - sh)) : b0[q]) & pmask;
-                if (in[q] && !pbits) { ++n_drop; continue; }
-                if (in[q]) ++n_prob; else ++n_unpr;
-                const u64 min_intv = ((u64)hi[q].x | (u64)hi[q].y << 32) + 1;
-                if (m < LH_P2_SPLIT)
-                    ent[m * 256 + threadIdx.x] = (u64)(uint32_t)r | (u64)xm[q] << LH_P2E_XM | min_intv << LH_P2E_MIN | (in[q] ? pbits << LH_P2E_PBITS : LH_P2E_UNPROBED);
-                ++m;
-            }
+        for (int k0 = 0; k0 < on; k0 += 4) {
+            j.load(iv, k0, on);
+            j.classify(ix, o, seq, off, k0, on);
+            j.fetch_bits(ix);
+            j.settle(r, ent);
         }
-        if (m > LH_P2_SPLIT) { share = 1; m = LH_P2_SPLIT; n_prob = n_unpr = 0; }   // (a share's lane judges its calls again: only the dropped ones count here)
+        j.close();
     }
-    const int incl = wave_scan_add_i32(m);
-    const int tot = wave_readlane(incl, 63);
-    int basep = 0;
-    if (lane == 0 && tot) basep = atomicAdd(n_tasks, tot);
-    basep = wave_readlane(basep, 0);
-    for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = share ? p2_share_entry(r, j, m) : ent[j * 256 + threadIdx.x];
-    const int t_drop = wave_sum_i32(n_drop), t_prob = wave_sum_i32(n_prob), t_unpr = wave_sum_i32(n_unpr), t_sh = __popcll(__ballot(share));
-    if (lane == 0) {
-        if (t_drop) atomicAdd(&LH_CTR(calls)->dropped, (u64)t_drop);
-        if (t_prob) atomicAdd(&LH_CTR(calls)->probed, (u64)t_prob);
-        if (t_unpr) atomicAdd(&LH_CTR(calls)->unprobed, (u64)t_unpr);
-        if (t_sh) atomicAdd(&LH_CTR(calls)->shares, (u64)t_sh);
-    }
+    j.flush(r, lane, ent, tasks, n_tasks, calls);
 }
 // the listers' counts in two words for the host: dropped | probed << 32, unprobed | shares << 32 (a read-out: each count modulo 2^32)
 __global__ void __launch_bounds__(64) k_peek_k1(const i64* __restrict__ seeds, const int32_t* __restrict__ big_asked, const P2Calls* __restrict__ calls, i64* __restrict__ dst_host) {
@@ -1372,160 +1404,19 @@ __device__ __forceinline__ int dev_seed_count(const DOpts& o, u64 s) {
     u64 c = (s + step - 1) / step;
     return (int)(c < (u64)o.max_occ ? c : (u64)o.max_occ);
 }
-// PASS 3 IN LOCKSTEP, one thread per read (new in r03).  bwt_seed_strategy1 is a forward-only loop — no interval lists, no sweeps — so
-// it needs no state machine: every thread walks its own read, the threads of a wave in the same short loop.  Same shortcuts as the
-// pass-3 state machine (k_smem_pass<3>): a walk that starts inside one of the read's unique SMEMs is one PLCP byte (P3TEXT), any other
-// takes its first bases from the k-mer tree table and goes on through the occurrence table.  Measured: 0.1 G wave-instructions at
-// ~40 active lanes for what cost the state machine 1.2 G at 24.
-__global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_reads, const uint32_t* __restrict__ q4, const i64* __restrict__ seq_off, DIntv* __restrict__ intv_out,
-                                                       int32_t* __restrict__ n_intv, int32_t* __restrict__ status, DCounters* __restrict__ ctr,
-                                                       int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep, int32_t* __restrict__ fin_list, int32_t* __restrict__ fin_count) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
-    const PEnt* const kt = (const PEnt*)ix.ktree;
-    const int ktl = kt ? ix.ktree_levels : 0;
-    const int Lw = o.min_seed_len + 1;
-    const bool text_ok = ix.isa != nullptr && ix.plcp != nullptr && o.max_mem_intv > 1;
-    unsigned n_ext = 0, n_exec = 0, n_kt = 0;
-    // one word of state beside the walk (a second one costs this kernel a wave per SIMD).  Bit 31: an interval found no slot.  Below it, if seed_cnt is given: the read's
-    // seeds while none of its intervals has more than max_occ occurrences (every occurrence is a seed then: dev_seed_count without its 64-bit divisions); an interval
-    // that has adds LH_CNT_REP, and the read is listed for k_smem_fin, which counts it properly
-    uint32_t cnt = 0;
-    int fin = 0;
-    if (r < n_reads) {
-        const i64 off = seq_off[r];
-        int len = (int)(seq_off[r + 1] - off);
-        int on = n_intv[r];
-        if (len > LH_MAXLEN) len = 0;
-        DIntv* out = intv_out + (size_t)r * LH_MAX_INTV;
-#define QN(i_) ((int)(dev_nib8(q4, off + (i_)) & 0xf))
-        if (len >= o.min_seed_len && o.max_mem_intv > 0) {
-            // the read's two longest unique SMEMs [us, ue) and their text positions (pass 1 stored them by position; a row is one suffix-array read)
-            int us0 = 0, ue0 = 0, us1 = 0, ue1 = 0;
-            u64 up0 = 0, up1 = 0;
-            if (text_ok)
-                for (int k = 0; k < on; ++k) {
-                    const DIntv p = out[k];
-                    if (seed_cnt) cnt += dev_cnt_acc(o, p.x2);
-                    const int ps = (int)(p.info >> 32), pe = (int)(uint32_t)p.info;
-                    if (p.x2 != 1 || pe - ps < Lw) continue;
-                    if (pe - ps > ue0 - us0) { us1 = us0; ue1 = ue0; up1 = up0; us0 = ps; ue0 = pe; up0 = p.x0; }
-                    else if (pe - ps > ue1 - us1) { us1 = ps; ue1 = pe; up1 = p.x0; }
-                }
-            else if (seed_cnt)
-                for (int k = 0; k < on; ++k) cnt += dev_cnt_acc(o, out[k].x2);
-            if (ue0 > us0) up0 = (up0 & LH_POSF) ? up0 & ~LH_POSF : ix.sa[up0];
-            if (ue1 > us1) up1 = (up1 & LH_POSF) ? up1 & ~LH_POSF : ix.sa[up1];
-            int x = 0, notext = 0;
-            while (x < len) {
-                if (QN(x) > 3) { ++x; continue; }
-                const int in0 = x >= us0 && x + Lw <= ue0, in1 = x >= us1 && x + Lw <= ue1;
-                if (text_ok && !notext && (in0 || in1)) {   // by text: unique iff the suffix there shares fewer than Lw bases with every other one
-                    const i64 tp = in0 ? (i64)up0 + (x - us0) : (i64)up1 + (x - us1);
-                    if ((int)ix.plcp[tp] < Lw) {
-                        if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
-                        else {
-                            DIntv m; m.x0 = LH_POSF | (u64)tp; m.x1 = 0; m.x2 = 1; m.info = (u64)x << 32 | (u64)(x + Lw); out[on++] = m;
-                            if (seed_cnt) cnt += dev_cnt_acc(o, 1);
-                        }
-                        n_ext += (unsigned)(Lw - 1);
-                        x += Lw;
-                        continue;
-                    }
-                    notext = 1;   // it occurs again: the walk as written, from x
-                }
-                notext = 0;
-                // bwt_seed_strategy1 from x
-                DIntv c = dev_set_intv(ix, QN(x));
-                int i = x + 1;
-                uint32_t fcode = (uint32_t)QN(x);
-                if (ktl > 1 && x + ktl <= len && o.min_seed_len >= ktl) {   // the walk's first ktl bases from the tree's deepest level (none of those steps can end it)
-                    uint32_t w0 = dev_nib8(q4, off + x), w1 = dev_nib8(q4, off + x + 8);
-                    uint32_t m0 = w0, m1 = w1;
-                    if (ktl < 8) { m0 &= (1u << (4 * ktl)) - 1u; m1 = 0; }
-                    else if (ktl < 16) m1 &= (1u << (4 * (ktl - 8))) - 1u;
-                    if (!((m0 | m1) & 0x44444444u)) {
-                        uint32_t ca = w0 & 0x33333333u, cb = w1 & 0x33333333u;
-                        ca = (ca | ca >> 2) & 0x0f0f0f0fu; ca = (ca | ca >> 4) & 0x00ff00ffu; ca = (ca | ca >> 8) & 0xffffu;
-                        cb = (cb | cb >> 2) & 0x0f0f0f0fu; cb = (cb | cb >> 4) & 0x00ff00ffu; cb = (cb | cb >> 8) & 0xffffu;
-                        const uint32_t code = (ca | cb << 16) & (ktl >= 16 ? 0xffffffffu : (1u << (2 * ktl)) - 1u);
-                        const PEnt te = kt[(((1ull << (2 * ktl)) - 4) / 3) + code];
-                        c.x0 = PE_X0(te); c.x1 = PE_X1(te); c.x2 = PE_X2(te);
-                        n_ext += (unsigned)(ktl - 1);
-                        i = x + ktl;
-                    }
-                }
-                int nx = len;   // where the next walk starts
-                for (; i < len; ++i) {
-                    const int b = QN(i);
-                    if (b > 3) { nx = i + 1; break; }
-                    DIntv ok;
-                    const int lnew = i + 1 - x;
-                    if (lnew <= ktl) {   // a short match: its interval is the tree's entry
-                        fcode |= (uint32_t)b << (2 * (lnew - 1));
-                        const PEnt te = kt[(((1ull << (2 * lnew)) - 4) / 3) + fcode];
-                        ok.x0 = PE_X0(te); ok.x1 = PE_X1(te); ok.x2 = PE_X2(te); ok.info = 0;
-                        ++n_kt;
-                    } else { ok = dev_extend_c(ix, c, 3 - b, 0); ++n_exec; }
-                    ++n_ext;
-                    if (ok.x2 < (u64)o.max_mem_intv && i - x >= o.min_seed_len) {
-                        if (ok.x2 > 0) {
-                            if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
-                            else {
-                                ok.info = (u64)x << 32 | (u64)(i + 1); out[on++] = ok;
-                                if (seed_cnt) cnt += dev_cnt_acc(o, ok.x2);
-                            }
-                        }
-                        nx = i + 1;
-                        break;
-                    }
-                    c = ok;
-                }
-                x = nx;
-            }
-        } else if (seed_cnt)   // a read pass 3 does not walk (no bases, too short, too long) is counted all the same
-            for (int k = 0; k < on; ++k) cnt += dev_cnt_acc(o, out[k].x2);
-#undef QN
-        if (cnt & LH_CNT_OVF) status[r] |= LH_ST_INTV_OVERFLOW;
-        n_intv[r] = on;
-        if (seed_cnt) {
-            // the counts k_smem_fin would find.  K2 ranks a read of at most 16 intervals inside its group (k_seed.h); the others, and those whose count and l_rep need
-            // the sampling of an interval above max_occ, are listed for k_smem_fin, which overwrites both words.  (A read that overflowed may be listed too:
-            // k_smem_fin skips it once it has a big-slab slot, and k_smem_fin_big writes its words)
-            seed_cnt[r] = (int)(cnt & (LH_CNT_REP - 1)); l_rep[r] = 0;
-            fin = on > 16 || (cnt & ~LH_CNT_OVF) >= LH_CNT_REP;
-        }
-    }
-    if (seed_cnt) {   // one append per wave, the lanes at their prefix
-        const u64 m = __ballot(fin);
-        int base = 0;
-        if (lane == 0 && m) base = atomicAdd(fin_count, __popcll(m));
-        base = wave_readlane(base, 0);
-        if (fin) fin_list[base + lanes_below(m, lane)] = r;
-    }
-    if (ctr) {
-        unsigned t1 = (unsigned)wave_sum_i32((int)n_ext), t2 = (unsigned)wave_sum_i32((int)n_exec), t3 = (unsigned)wave_sum_i32((int)n_kt);
-        if (lane == 0 && t1) { atomicAdd(&LH_CTR(ctr)->n_ext, (u64)t1); atomicAdd(&LH_CTR(ctr)->n_ext_exec[2], (u64)t2); atomicAdd(&LH_CTR(ctr)->n_ktree[2], (u64)t3); }
-    }
-}
-// PASS 2'S PROBE AND PASS 3 IN ONE LOCKSTEP KERNEL (r15), one thread per read, behind pass 1.  k_p2_probe and k_smem_p3_lock both began with the read's pass-1
-// intervals — the probe four at a time to judge the re-seeding calls, pass 3 one dependent load after the other to find the two longest unique SMEMs and to count
-// the seeds — and pass 3 came after pass 2 only to count pass 2's intervals: its walks use pass 1's unique SMEMs alone (a call of pass 2 has min_intv >= 2: it never
-// emits a unique interval).  mem_collect_intv appends the three passes to one vector that is sorted afterwards, and here K2 ranks a read's intervals by (info, slot)
-// with equal info meaning identical intervals: the order of the slots is free.  So one scan serves both, pass 3 appends right behind pass 1 (slots n1, n1 + 1, ...),
-// and pass 2's calls take their slots behind it from the read's counter, each adding its own occurrences to the read's count word (P2_COUNT_ADD).  The word is left
-// raw in seed_cnt[r] — the LH_CNT_REP sums and LH_CNT_OVF — for k_p2_close, which runs after pass 2 and writes what k_smem_p3_lock writes.
-// The prologue and the probe part are k_p2_probe's, the walk part is k_smem_p3_lock's loop: see there.
 #ifdef LH_P3_KINDS   // development aid (-DLH_P3_KINDS, not shipped; run_front prints and clears it): the batch's intervals per pass and pass 3's walks by kind
 // [0] reads, [1] intervals of pass 1, [2] of pass 3, [3] in the end (k_p2_close); [4] walks decided by text; then per kind k = 0 .. 2 — a table walk that starts
 // inside a third-or-later unique SMEM of pass 1, any other table walk, a final walk that cannot emit (x + min_seed_len >= len) — [5 + k] walks, [8 + k] executed
-// extends, [11 + k] tree reads
+// extends, [11 + k] tree reads.  k_p23_lock's walks are the ones counted (P3K_FLUSH)
 __device__ unsigned long long lh_p3_kinds[16];
 #define P3K_DECL() unsigned k3_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int kk_ = 0; unsigned ke_ = 0, kt_ = 0;
+#define P3K_PARAMS , unsigned* k3_, int& kk_, unsigned& ke_, unsigned& kt_, int n1_
+#define P3K_ARGS(n1) , k3_, kk_, ke_, kt_, (int)(n1)
 #define P3K_ADD(i_, v_) k3_[i_] += (unsigned)(v_);
 #define P3K_BEGIN()                                                                                                          \
     {                                                                                                                        \
         kk_ = 1; ke_ = n_exec; kt_ = n_kt;                                                                                   \
-        for (int k_ = 0; k_ < (int)n_pass1[r]; ++k_) {                                                                       \
+        for (int k_ = 0; k_ < n1_; ++k_) {                                                                                   \
             const DIntv p_ = out[k_];                                                                                        \
             const int ps_ = (int)(p_.info >> 32), pe_ = (int)(uint32_t)p_.info;                                              \
             if (p_.x2 == 1 && !in0 && !in1 && x >= ps_ && x + Lw <= pe_) kk_ = 0;                                            \
@@ -1537,28 +1428,201 @@ __device__ unsigned long long lh_p3_kinds[16];
     for (int i_ = 0; i_ < 14; ++i_) { const unsigned t_ = (unsigned)wave_sum_i32((int)k3_[i_]); if (lane == 0 && t_) atomicAdd(&lh_p3_kinds[i_], (unsigned long long)t_); }
 #else
 #define P3K_DECL()
+#define P3K_PARAMS
+#define P3K_ARGS(n1)
 #define P3K_ADD(i_, v_)
 #define P3K_BEGIN()
 #define P3K_END()
 #define P3K_FLUSH()
 #endif
+// PASS 3 IN LOCKSTEP (r03): its pieces, for k_smem_p3_lock and k_p23_lock.  bwt_seed_strategy1 is a forward-only loop — no interval lists, no sweeps — so it needs no
+// state machine: every thread walks its own read, the threads of a wave in the same short loop.  Measured: 0.1 G wave-instructions at ~40 active lanes for what cost
+// the state machine 1.2 G at 24.
+__device__ __forceinline__ bool p3_text_ok(const DIndex& ix, const DOpts& o) { return ix.isa != nullptr && ix.plcp != nullptr && o.max_mem_intv > 1; }
+// The choice among a read's pass-1 intervals, offered in their order: the two longest unique SMEMs [us, ue) of at least Lw bases, packed a byte each
+// (us0 | ue0 << 8 | us1 << 16 | ue1 << 24: k_smem_pass's uspan), and their x0 as pass 1 stored it (a text position, or a row).  Strict >: the first of equals wins.
+__device__ __forceinline__ void p3_pick(int Lw, u64 x0, u64 x2, int ps, int pe, uint32_t& uspan, u64& up0, u64& up1) {
+    if (x2 != 1 || pe - ps < Lw) return;
+    const int l0 = (int)((uspan >> 8) & 0xff) - (int)(uspan & 0xff), l1 = (int)(uspan >> 24) - (int)((uspan >> 16) & 0xff);
+    const uint32_t sp = (uint32_t)ps | (uint32_t)pe << 8;
+    uint32_t us = uspan;   // (locals, as p3_walk's: "up0 = x0 else up1 = x0" through references becomes one store at a chosen address)
+    u64 p0 = up0, p1 = up1;
+    if (pe - ps > l0) { us = us << 16 | sp; p1 = p0; p0 = x0; }
+    else if (pe - ps > l1) { us = (us & 0xffffu) | sp << 16; p1 = x0; }
+    uspan = us; up0 = p0; up1 = p1;
+}
+// The walks over one read of len bases (0: none), appended at out[on ...].  Same shortcuts as the pass-3 state machine (k_smem_pass<3>): a walk that starts inside one of
+// the two unique SMEMs of uspan (text positions up0, up1) is one PLCP byte (P3TEXT), any other takes its first bases from the k-mer tree table and goes on through the
+// occurrence table.  ONE word of state beside the walk (a second one costs the kernels a wave per SIMD), cnt.  Bit 31: an interval found no slot.  Below it: the read's
+// seeds while none of its intervals has more than max_occ occurrences (every occurrence is a seed then: dev_seed_count without its 64-bit divisions); an interval that
+// has adds LH_CNT_REP, and the read is listed for k_smem_fin, which counts it properly.
+__device__ __forceinline__ void p3_walk(const DIndex& ix, const DOpts& o, const uint32_t* __restrict__ q4, i64 off, int len, DIntv* out, int& on_io, uint32_t uspan, u64 up0, u64 up1,
+                                        uint32_t& cnt_io, unsigned& ext_io, unsigned& exec_io, unsigned& kt_io P3K_PARAMS) {
+    // (worked on as locals and handed back at the end: through a reference the compiler folds "++n_kt else ++n_exec" into one add at a chosen address, and the counters
+    // stay in scratch)
+    int on = on_io;
+    uint32_t cnt = cnt_io;
+    unsigned n_ext = ext_io, n_exec = exec_io, n_kt = kt_io;
+    const PEnt* const kt = (const PEnt*)ix.ktree;
+    const int ktl = kt ? ix.ktree_levels : 0;
+    const int Lw = o.min_seed_len + 1;
+    const bool text_ok = p3_text_ok(ix, o);
+#define QN(i_) ((int)(dev_nib8(q4, off + (i_)) & 0xf))
+#define P3_US0 ((int)(uspan & 0xff))   // (unpacked where they are used: the spans stay one register)
+#define P3_UE0 ((int)((uspan >> 8) & 0xff))
+#define P3_US1 ((int)((uspan >> 16) & 0xff))
+#define P3_UE1 ((int)(uspan >> 24))
+    int x = 0, notext = 0;
+    while (x < len) {
+        if (QN(x) > 3) { ++x; continue; }
+        const int in0 = x >= P3_US0 && x + Lw <= P3_UE0, in1 = x >= P3_US1 && x + Lw <= P3_UE1;
+        if (text_ok && !notext && (in0 || in1)) {   // by text: unique iff the suffix there shares fewer than Lw bases with every other one
+            const i64 tp = in0 ? (i64)up0 + (x - P3_US0) : (i64)up1 + (x - P3_US1);
+            if ((int)ix.plcp[tp] < Lw) {
+                if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
+                else {
+                    DIntv mm; mm.x0 = LH_POSF | (u64)tp; mm.x1 = 0; mm.x2 = 1; mm.info = (u64)x << 32 | (u64)(x + Lw); out[on++] = mm;
+                    cnt += dev_cnt_acc(o, 1);
+                }
+                n_ext += (unsigned)(Lw - 1);
+                x += Lw;
+                P3K_ADD(4, 1)
+                continue;
+            }
+            notext = 1;   // it occurs again: the walk as written, from x
+        }
+        notext = 0;
+        // bwt_seed_strategy1 from x
+        P3K_BEGIN()
+        DIntv c = dev_set_intv(ix, QN(x));
+        int i = x + 1;
+        uint32_t fcode = (uint32_t)QN(x);
+        if (ktl > 1 && x + ktl <= len && o.min_seed_len >= ktl) {   // the walk's first ktl bases from the tree's deepest level (none of those steps can end it)
+            uint32_t w0 = dev_nib8(q4, off + x), w1 = dev_nib8(q4, off + x + 8);
+            uint32_t m0 = w0, m1 = w1;
+            if (ktl < 8) { m0 &= (1u << (4 * ktl)) - 1u; m1 = 0; }
+            else if (ktl < 16) m1 &= (1u << (4 * (ktl - 8))) - 1u;
+            if (!((m0 | m1) & 0x44444444u)) {
+                uint32_t ca = w0 & 0x33333333u, cb = w1 & 0x33333333u;
+                ca = (ca | ca >> 2) & 0x0f0f0f0fu; ca = (ca | ca >> 4) & 0x00ff00ffu; ca = (ca | ca >> 8) & 0xffffu;
+                cb = (cb | cb >> 2) & 0x0f0f0f0fu; cb = (cb | cb >> 4) & 0x00ff00ffu; cb = (cb | cb >> 8) & 0xffffu;
+                const uint32_t code = (ca | cb << 16) & (ktl >= 16 ? 0xffffffffu : (1u << (2 * ktl)) - 1u);
+                const PEnt te = kt[(((1ull << (2 * ktl)) - 4) / 3) + code];
+                c.x0 = PE_X0(te); c.x1 = PE_X1(te); c.x2 = PE_X2(te);
+                n_ext += (unsigned)(ktl - 1);
+                i = x + ktl;
+            }
+        }
+        int nx = len;   // where the next walk starts
+        for (; i < len; ++i) {
+            const int b = QN(i);
+            if (b > 3) { nx = i + 1; break; }
+            DIntv ok;
+            const int lnew = i + 1 - x;
+            if (lnew <= ktl) {   // a short match: its interval is the tree's entry
+                fcode |= (uint32_t)b << (2 * (lnew - 1));
+                const PEnt te = kt[(((1ull << (2 * lnew)) - 4) / 3) + fcode];
+                ok.x0 = PE_X0(te); ok.x1 = PE_X1(te); ok.x2 = PE_X2(te); ok.info = 0;
+                ++n_kt;
+            } else { ok = dev_extend_c(ix, c, 3 - b, 0); ++n_exec; }
+            ++n_ext;
+            if (ok.x2 < (u64)o.max_mem_intv && i - x >= o.min_seed_len) {
+                if (ok.x2 > 0) {
+                    if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
+                    else {
+                        ok.info = (u64)x << 32 | (u64)(i + 1); out[on++] = ok;
+                        cnt += dev_cnt_acc(o, ok.x2);
+                    }
+                }
+                nx = i + 1;
+                break;
+            }
+            c = ok;
+        }
+        x = nx;
+        P3K_END()
+    }
+    on_io = on; cnt_io = cnt; ext_io = n_ext; exec_io = n_exec; kt_io = n_kt;
+#undef QN
+#undef P3_US0
+#undef P3_UE0
+#undef P3_US1
+#undef P3_UE1
+}
+// the walks' counters, by every thread of the block
+__device__ __forceinline__ void p3_flush_ctr(DCounters* __restrict__ ctr, int lane, unsigned n_ext, unsigned n_exec, unsigned n_kt) {
+    if (!ctr) return;
+    unsigned t1 = (unsigned)wave_sum_i32((int)n_ext), t2 = (unsigned)wave_sum_i32((int)n_exec), t3 = (unsigned)wave_sum_i32((int)n_kt);
+    if (lane == 0 && t1) { atomicAdd(&LH_CTR(ctr)->n_ext, (u64)t1); atomicAdd(&LH_CTR(ctr)->n_ext_exec[2], (u64)t2); atomicAdd(&LH_CTR(ctr)->n_ktree[2], (u64)t3); }
+}
+// The end of a read with `on` intervals in its regular slots and the count word cnt, once nothing appends to them any more: the word's overflow bit becomes the read's
+// status bit and, where the seeds are counted, the counts k_smem_fin would find.  K2 ranks a read of at most 16 intervals inside its group (k_seed.h);
+// the others, and those whose count and l_rep need the sampling of an interval above max_occ, are to be listed for k_smem_fin, which overwrites both words: returned.
+// (A read that overflowed may be listed too: k_smem_fin skips it once it has a big-slab slot, and k_smem_fin_big writes its words)
+__device__ __forceinline__ int p3_read_end(int r, int on, uint32_t cnt, bool counted, int32_t* __restrict__ status, int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep) {
+    if (cnt & LH_CNT_OVF) status[r] |= LH_ST_INTV_OVERFLOW;
+    if (!counted) return 0;
+    seed_cnt[r] = (int)(cnt & (LH_CNT_REP - 1)); l_rep[r] = 0;
+    return on > 16 || (cnt & ~LH_CNT_OVF) >= LH_CNT_REP;
+}
+// ... and k_smem_fin's list, by every thread of the block: one append per wave, the lanes at their prefix
+__device__ __forceinline__ void p3_fin_append(int fin, int r, int lane, int32_t* __restrict__ fin_list, int32_t* __restrict__ fin_count) {
+    const u64 m = __ballot(fin);
+    int base = 0;
+    if (lane == 0 && m) base = atomicAdd(fin_count, __popcll(m));
+    base = wave_readlane(base, 0);
+    if (fin) fin_list[base + lanes_below(m, lane)] = r;
+}
+// pass 3 as a kernel of its own, behind pass 2 (every sequence but the default one), one thread per read: one dependent load after the other over the read's intervals —
+// pass 1's for the choice, all of them for the count — the two SMEMs' suffix-array reads (a row is one read; a position needs none), the walks, the end of the read.
+// seed_cnt == nullptr (the lane-per-seed K2, the trace build): no counts and no list, k_smem_fin then runs over every read.
+__global__ void __launch_bounds__(256) k_smem_p3_lock(DIndex ix, DOpts o, int n_reads, const uint32_t* __restrict__ q4, const i64* __restrict__ seq_off, DIntv* __restrict__ intv_out,
+                                                       int32_t* __restrict__ n_intv, int32_t* __restrict__ status, DCounters* __restrict__ ctr,
+                                                       int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep, int32_t* __restrict__ fin_list, int32_t* __restrict__ fin_count) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
+    unsigned n_ext = 0, n_exec = 0, n_kt = 0;
+    int fin = 0;
+    P3K_DECL()
+    if (r < n_reads) {
+        const i64 off = seq_off[r];
+        int len = (int)(seq_off[r + 1] - off);
+        if (len > LH_MAXLEN || len < o.min_seed_len || o.max_mem_intv <= 0) len = 0;   // (no bases, too short, too long: not walked, and counted all the same)
+        int on = n_intv[r];
+        DIntv* out = intv_out + (size_t)r * LH_MAX_INTV;
+        const bool pick = p3_text_ok(ix, o) && len > 0;
+        uint32_t uspan = 0, cnt = 0;
+        u64 up0 = 0, up1 = 0;
+        if (pick || seed_cnt)
+            for (int k = 0; k < on; ++k) {
+                const DIntv p = out[k];
+                cnt += dev_cnt_acc(o, p.x2);
+                if (pick) p3_pick(o.min_seed_len + 1, p.x0, p.x2, (int)(p.info >> 32), (int)(uint32_t)p.info, uspan, up0, up1);
+            }
+        if (uspan & 0xffffu) up0 = (up0 & LH_POSF) ? up0 & ~LH_POSF : ix.sa[up0];
+        if (uspan >> 16) up1 = (up1 & LH_POSF) ? up1 & ~LH_POSF : ix.sa[up1];
+        p3_walk(ix, o, q4, off, len, out, on, uspan, up0, up1, cnt, n_ext, n_exec, n_kt P3K_ARGS(on));
+        n_intv[r] = on;
+        fin = p3_read_end(r, on, cnt, seed_cnt != nullptr, status, seed_cnt, l_rep);
+    }
+    if (seed_cnt) p3_fin_append(fin, r, lane, fin_list, fin_count);
+    p3_flush_ctr(ctr, lane, n_ext, n_exec, n_kt);
+}
+// PASS 2'S PROBE AND PASS 3 IN ONE LOCKSTEP KERNEL (r15), one thread per read, behind pass 1: the default.  The judge and pass 3 both begin with the read's pass-1
+// intervals, and pass 3 came after pass 2 only to count pass 2's intervals: its walks use pass 1's unique SMEMs alone (a call of pass 2 has min_intv >= 2: it never
+// emits a unique interval).  mem_collect_intv appends the three passes to one vector that is sorted afterwards, and here K2 ranks a read's intervals by (info, slot)
+// with equal info meaning identical intervals: the order of the slots is free.  So one scan serves both — the judge's four intervals at a time, pass 3's choice and
+// count from the registers the judge holds anyway — pass 3 appends right behind pass 1 (slots n1, n1 + 1, ...), and pass 2's calls take their slots behind it from
+// the read's counter, each adding its own occurrences to the read's count word (P2_COUNT_ADD).  The word is left raw in seed_cnt[r] — the LH_CNT_REP sums and
+// LH_CNT_OVF — for k_p2_close, which runs after pass 2 and ends the read.
 __global__ void __launch_bounds__(256, 6) k_p23_lock(DIndex ix, DOpts o, int n_reads, const uint8_t* __restrict__ seq, const uint32_t* __restrict__ q4, const i64* __restrict__ seq_off,
                                                    DIntv* __restrict__ intv_out, int32_t* __restrict__ n_intv, DCounters* __restrict__ ctr, int32_t* __restrict__ seed_cnt,
                                                    u64* __restrict__ tasks, int32_t* __restrict__ n_tasks, int32_t* __restrict__ n_pass1, P2Calls* __restrict__ calls) {
-    __shared__ u64 ent[LH_P2_SPLIT * 256];   // entry j of thread t at ent[j * 256 + t]
+    __shared__ u64 ent[LH_P2_SPLIT * 256];
     const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
-    const bool probe = ix.bloom1 != nullptr && ix.rep_t != nullptr && o.min_seed_len >= LH_BLOOM_K;
-    const int split_len = (int)(o.min_seed_len * o.split_factor + .499);
-#ifdef LH_P2_PROBE_WEAK
-    const u64 pmask = (1ull << (LH_BLOOM_K - 1)) - 1;
-#else
-    const u64 pmask = (1ull << LH_BLOOM_K) - 1;
-#endif
+    P2Judge j(ix, o);
     const int Lw = o.min_seed_len + 1;
-    const bool text_ok = ix.isa != nullptr && ix.plcp != nullptr && o.max_mem_intv > 1;
-    int m = 0, n_drop = 0, n_prob = 0, n_unpr = 0, share = 0;
-    // what the walk part needs of the scan: the read, its length (0: not walked), its intervals so far, the two longest unique SMEMs [us, ue) packed a byte each
-    // (us0 | ue0 << 8 | us1 << 16 | ue1 << 24: k_smem_pass's uspan) with their text positions, and the count word
+    const bool text_ok = p3_text_ok(ix, o);
+    // what the walks need of the scan: the read, its length (0: not walked), its intervals so far, pass 3's choice and the count word
     i64 off = 0;
     int len = 0, on = 0;
     uint32_t uspan = 0, cnt = 0;
@@ -1570,189 +1634,43 @@ __global__ void __launch_bounds__(256, 6) k_p23_lock(DIndex ix, DOpts o, int n_r
         on = n_intv[r] < LH_MAX_INTV ? n_intv[r] : LH_MAX_INTV;
         n_pass1[r] = on;
         const bool pick = text_ok && len > 0;
-        const uint4* const iv = (const uint4*)(intv_out + (size_t)r * LH_MAX_INTV);   // an interval: (x0, x1), (x2, info)
-        for (int k0 = 0; k0 < on; k0 += 4) {   // four intervals at a time: each step's loads are in flight together
-            uint2 lo[4];   // (x0 alone: neither part looks at x1)
-            uint4 hi[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                lo[q] = uint2{0, 0}; hi[q] = uint4{0, 0, 0, 0};
-                if (k0 + q < on) { lo[q] = *(const uint2*)&iv[2 * (k0 + q)]; hi[q] = iv[2 * (k0 + q) + 1]; }
-            }
-            // pass 3's choice in its order and with its tie rule (strict >: the first of equals wins), and the running count
+        const uint4* const iv = (const uint4*)(intv_out + (size_t)r * LH_MAX_INTV);
+        for (int k0 = 0; k0 < on; k0 += 4) {
+            j.load(iv, k0, on);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (k0 + q >= on) continue;
-                const int ps = (int)hi[q].w, pe = (int)hi[q].z;
-                const u64 x0 = (u64)lo[q].x | (u64)lo[q].y << 32, x2 = (u64)hi[q].x | (u64)hi[q].y << 32;
-                cnt += dev_cnt_acc(o, x2);
-                if (!pick || x2 != 1 || pe - ps < Lw) continue;
-                const int l0 = (int)((uspan >> 8) & 0xff) - (int)(uspan & 0xff), l1 = (int)(uspan >> 24) - (int)((uspan >> 16) & 0xff);
-                const uint32_t sp = (uint32_t)ps | (uint32_t)pe << 8;
-                if (pe - ps > l0) { uspan = uspan << 16 | sp; up1 = up0; up0 = x0; }
-                else if (pe - ps > l1) { uspan = (uspan & 0xffffu) | sp << 16; up1 = x0; }
+                cnt += dev_cnt_acc(o, j.x2(q));
+                if (pick) p3_pick(Lw, j.x0(q), j.x2(q), (int)j.hi[q].w, (int)j.hi[q].z, uspan, up0, up1);
             }
-            // the two SMEMs' suffix-array reads beside the probe's own: after the last four intervals the choice is made (a row is one read; a position needs none)
+            // the two SMEMs' suffix-array reads beside the judge's own: after the last four intervals the choice is made (a row is one read; a position needs none)
             const bool last = k0 + 4 >= on;
             u64 s0 = up0 & ~LH_POSF, s1 = up1 & ~LH_POSF;
             const bool rd0 = last && (uspan & 0xffffu) && !(up0 & LH_POSF), rd1 = last && (uspan >> 16) && !(up1 & LH_POSF);
             if (rd0) s0 = ix.sa[up0];
             if (rd1) s1 = ix.sa[up1];
-            bool call[4], in[4];
-            int xm[4], w0[4];
-            uint32_t base[4];
-            u64 pos[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int s = (int)hi[q].w, e = (int)hi[q].z;
-                const u64 x0 = (u64)lo[q].x | (u64)lo[q].y << 32, x2 = (u64)hi[q].x | (u64)hi[q].y << 32;
-                call[q] = k0 + q < on && e - s >= split_len && x2 <= (u64)o.split_width;   // long and rare
-                xm[q] = (s + e) >> 1; w0[q] = xm[q] - (LH_BLOOM_K - 1) - s;
-                in[q] = call[q] && probe && w0[q] >= 0 && xm[q] + LH_BLOOM_K <= e;   // the windows lie inside the SMEM
-                base[q] = 4; pos[q] = x0 & ~LH_POSF;
-                if (call[q]) base[q] = seq[off + xm[q]];
-                if (in[q] && !(x0 & LH_POSF)) pos[q] = ix.sa[x0];   // stored as rows: the first row's occurrence
-            }
-            u64 b0[4], b1[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                call[q] = call[q] && base[q] <= 3;   // bwt_smem1a returns at once on an ambiguous base: no call
-                in[q] = in[q] && call[q];
-                b0[q] = b1[q] = 0; pos[q] += (u64)w0[q];   // the first window's text position
-                if (in[q]) { b0[q] = ix.rep_t[pos[q] >> 6]; b1[q] = ix.rep_t[(pos[q] >> 6) + 1]; }
-            }
+            j.classify(ix, o, seq, off, k0, on);
+            j.fetch_bits(ix);
             if (last) { up0 = s0; up1 = s1; }   // from here on: text positions
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (!call[q]) continue;
-                const uint32_t sh = (uint32_t)(pos[q] & 63);
-                const u64 pbits = (sh ? (b0[q] >> sh) | (b1[q] << (64 - sh)) : b0[q]) & pmask;
-                if (in[q] && !pbits) { ++n_drop; continue; }
-                if (in[q]) ++n_prob; else ++n_unpr;
-                const u64 min_intv = ((u64)hi[q].x | (u64)hi[q].y << 32) + 1;
-                if (m < LH_P2_SPLIT)
-                    ent[m * 256 + threadIdx.x] = (u64)(uint32_t)r | (u64)xm[q] << LH_P2E_XM | min_intv << LH_P2E_MIN | (in[q] ? pbits << LH_P2E_PBITS : LH_P2E_UNPROBED);
-                ++m;
-            }
+            j.settle(r, ent);
         }
-        if (m > LH_P2_SPLIT) { share = 1; m = LH_P2_SPLIT; n_prob = n_unpr = 0; }   // (a share's lane judges its calls again: only the dropped ones count here)
+        j.close();
     }
-    {   // the list and the listers' counts, as k_p2_probe
-        const int incl = wave_scan_add_i32(m);
-        const int tot = wave_readlane(incl, 63);
-        int basep = 0;
-        if (lane == 0 && tot) basep = atomicAdd(n_tasks, tot);
-        basep = wave_readlane(basep, 0);
-        for (int j = 0; j < m; ++j) tasks[basep + incl - m + j] = share ? p2_share_entry(r, j, m) : ent[j * 256 + threadIdx.x];
-        const int t_drop = wave_sum_i32(n_drop), t_prob = wave_sum_i32(n_prob), t_unpr = wave_sum_i32(n_unpr), t_sh = __popcll(__ballot(share));
-        if (lane == 0) {
-            if (t_drop) atomicAdd(&LH_CTR(calls)->dropped, (u64)t_drop);
-            if (t_prob) atomicAdd(&LH_CTR(calls)->probed, (u64)t_prob);
-            if (t_unpr) atomicAdd(&LH_CTR(calls)->unprobed, (u64)t_unpr);
-            if (t_sh) atomicAdd(&LH_CTR(calls)->shares, (u64)t_sh);
-        }
-    }
-    // ---- pass 3: k_smem_p3_lock's walks, appended behind pass 1's intervals ----
-    const PEnt* const kt = (const PEnt*)ix.ktree;
-    const int ktl = kt ? ix.ktree_levels : 0;
+    j.flush(r, lane, ent, tasks, n_tasks, calls);
     unsigned n_ext = 0, n_exec = 0, n_kt = 0;
     P3K_DECL()
     if (r < n_reads) {
-        DIntv* out = intv_out + (size_t)r * LH_MAX_INTV;
-#define QN(i_) ((int)(dev_nib8(q4, off + (i_)) & 0xf))
-#define P23_US0 ((int)(uspan & 0xff))
-#define P23_UE0 ((int)((uspan >> 8) & 0xff))
-#define P23_US1 ((int)((uspan >> 16) & 0xff))
-#define P23_UE1 ((int)(uspan >> 24))
-        int x = 0, notext = 0;
         P3K_ADD(0, 1) P3K_ADD(1, on)
-        while (x < len) {
-            if (QN(x) > 3) { ++x; continue; }
-            const int in0 = x >= P23_US0 && x + Lw <= P23_UE0, in1 = x >= P23_US1 && x + Lw <= P23_UE1;
-            if (text_ok && !notext && (in0 || in1)) {   // by text: unique iff the suffix there shares fewer than Lw bases with every other one
-                const i64 tp = in0 ? (i64)up0 + (x - P23_US0) : (i64)up1 + (x - P23_US1);
-                if ((int)ix.plcp[tp] < Lw) {
-                    if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
-                    else {
-                        DIntv mm; mm.x0 = LH_POSF | (u64)tp; mm.x1 = 0; mm.x2 = 1; mm.info = (u64)x << 32 | (u64)(x + Lw); out[on++] = mm;
-                        cnt += dev_cnt_acc(o, 1);
-                    }
-                    n_ext += (unsigned)(Lw - 1);
-                    x += Lw;
-                    P3K_ADD(4, 1)
-                    continue;
-                }
-                notext = 1;   // it occurs again: the walk as written, from x
-            }
-            notext = 0;
-            // bwt_seed_strategy1 from x
-            P3K_BEGIN()
-            DIntv c = dev_set_intv(ix, QN(x));
-            int i = x + 1;
-            uint32_t fcode = (uint32_t)QN(x);
-            if (ktl > 1 && x + ktl <= len && o.min_seed_len >= ktl) {   // the walk's first ktl bases from the tree's deepest level (none of those steps can end it)
-                uint32_t w0 = dev_nib8(q4, off + x), w1 = dev_nib8(q4, off + x + 8);
-                uint32_t m0 = w0, m1 = w1;
-                if (ktl < 8) { m0 &= (1u << (4 * ktl)) - 1u; m1 = 0; }
-                else if (ktl < 16) m1 &= (1u << (4 * (ktl - 8))) - 1u;
-                if (!((m0 | m1) & 0x44444444u)) {
-                    uint32_t ca = w0 & 0x33333333u, cb = w1 & 0x33333333u;
-                    ca = (ca | ca >> 2) & 0x0f0f0f0fu; ca = (ca | ca >> 4) & 0x00ff00ffu; ca = (ca | ca >> 8) & 0xffffu;
-                    cb = (cb | cb >> 2) & 0x0f0f0f0fu; cb = (cb | cb >> 4) & 0x00ff00ffu; cb = (cb | cb >> 8) & 0xffffu;
-                    const uint32_t code = (ca | cb << 16) & (ktl >= 16 ? 0xffffffffu : (1u << (2 * ktl)) - 1u);
-                    const PEnt te = kt[(((1ull << (2 * ktl)) - 4) / 3) + code];
-                    c.x0 = PE_X0(te); c.x1 = PE_X1(te); c.x2 = PE_X2(te);
-                    n_ext += (unsigned)(ktl - 1);
-                    i = x + ktl;
-                }
-            }
-            int nx = len;   // where the next walk starts
-            for (; i < len; ++i) {
-                const int b = QN(i);
-                if (b > 3) { nx = i + 1; break; }
-                DIntv ok;
-                const int lnew = i + 1 - x;
-                if (lnew <= ktl) {   // a short match: its interval is the tree's entry
-                    fcode |= (uint32_t)b << (2 * (lnew - 1));
-                    const PEnt te = kt[(((1ull << (2 * lnew)) - 4) / 3) + fcode];
-                    ok.x0 = PE_X0(te); ok.x1 = PE_X1(te); ok.x2 = PE_X2(te); ok.info = 0;
-                    ++n_kt;
-                } else { ok = dev_extend_c(ix, c, 3 - b, 0); ++n_exec; }
-                ++n_ext;
-                if (ok.x2 < (u64)o.max_mem_intv && i - x >= o.min_seed_len) {
-                    if (ok.x2 > 0) {
-                        if (on >= LH_MAX_INTV) cnt |= LH_CNT_OVF;
-                        else {
-                            ok.info = (u64)x << 32 | (u64)(i + 1); out[on++] = ok;
-                            cnt += dev_cnt_acc(o, ok.x2);
-                        }
-                    }
-                    nx = i + 1;
-                    break;
-                }
-                c = ok;
-            }
-            x = nx;
-            P3K_END()
-        }
-#undef QN
-#undef P23_US0
-#undef P23_UE0
-#undef P23_US1
-#undef P23_UE1
+        p3_walk(ix, o, q4, off, len, intv_out + (size_t)r * LH_MAX_INTV, on, uspan, up0, up1, cnt, n_ext, n_exec, n_kt P3K_ARGS(n_pass1[r]));
         P3K_ADD(2, on - n_pass1[r])
         n_intv[r] = on;             // pass 2's calls go on from here
         seed_cnt[r] = (int)cnt;     // raw: k_p2_close finishes it
     }
     P3K_FLUSH()
-    if (ctr) {
-        unsigned t1 = (unsigned)wave_sum_i32((int)n_ext), t2 = (unsigned)wave_sum_i32((int)n_exec), t3 = (unsigned)wave_sum_i32((int)n_kt);
-        if (lane == 0 && t1) { atomicAdd(&LH_CTR(ctr)->n_ext, (u64)t1); atomicAdd(&LH_CTR(ctr)->n_ext_exec[2], (u64)t2); atomicAdd(&LH_CTR(ctr)->n_ktree[2], (u64)t3); }
-    }
+    p3_flush_ctr(ctr, lane, n_ext, n_exec, n_kt);
 }
-// behind pass 2 over a list that followed k_p23_lock: what k_p2_clamp does (a read whose calls asked for more slots than it has: flagged by the call that was refused),
-// and the end of k_smem_p3_lock — the read's count word (pass 3's sums and those pass 2's calls added) becomes its seed count, l_rep 0; the reads with more than 16
-// intervals or one above max_occ are listed for k_smem_fin, which overwrites both words.  One thread per read, one append per wave.
+// behind pass 2 over a list that followed k_p23_lock, one thread per read: what k_p2_clamp does (a read whose calls asked for more slots than it has: flagged by the
+// call that was refused), and the end of the read from its count word — pass 3's sums and those pass 2's calls added.
 __global__ void __launch_bounds__(256) k_p2_close(int n_reads, int32_t* __restrict__ n_intv, int32_t* __restrict__ status, int32_t* __restrict__ seed_cnt, int32_t* __restrict__ l_rep,
                                                    int32_t* __restrict__ fin_list, int32_t* __restrict__ fin_count) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x, lane = LANE();
@@ -1760,10 +1678,7 @@ __global__ void __launch_bounds__(256) k_p2_close(int n_reads, int32_t* __restri
     if (r < n_reads) {
         int on = n_intv[r];
         if (on > LH_MAX_INTV) n_intv[r] = on = LH_MAX_INTV;
-        const uint32_t cnt = (uint32_t)seed_cnt[r];
-        if (cnt & LH_CNT_OVF) status[r] |= LH_ST_INTV_OVERFLOW;
-        seed_cnt[r] = (int)(cnt & (LH_CNT_REP - 1)); l_rep[r] = 0;
-        fin = on > 16 || (cnt & ~LH_CNT_OVF) >= LH_CNT_REP;
+        fin = p3_read_end(r, on, (uint32_t)seed_cnt[r], true, status, seed_cnt, l_rep);
 #ifdef LH_P3_KINDS
         atomicAdd(&lh_p3_kinds[3], (unsigned long long)on);
 #endif
@@ -1771,11 +1686,7 @@ __global__ void __launch_bounds__(256) k_p2_close(int n_reads, int32_t* __restri
 #ifdef LH_P23_NO_FIN_LIST   // test builds only: no read listed (the tests' reads of 17 intervals must then reach K2 unsorted)
     fin = 0;
 #endif
-    const u64 m = __ballot(fin);
-    int base = 0;
-    if (lane == 0 && m) base = atomicAdd(fin_count, __popcll(m));
-    base = wave_readlane(base, 0);
-    if (fin) fin_list[base + lanes_below(m, lane)] = r;
+    p3_fin_append(fin, r, lane, fin_list, fin_count);
 }
 
 // sort each read's intervals by info (rank sort; equal keys are identical intervals), seed counts, l_rep.  16 lanes per read

@@ -529,6 +529,41 @@ static int peek_seed_total(lh_context* c, int N) {
 }
 
 static inline int ext_long_min(int N);   // (lh_host_stage2.inc)
+// K1'S TAIL, what runs between pass 1 and k_smem_fin: the batch's plan.  A choice of path and never of result.
+// Pass 2 runs over a list (k_smem4.h: P2TASK).  By default the probe makes it: every re-seeding call judged in lockstep, the calls that can contribute listed one
+// by one with the probe's answer, a read with more than LH_P2_SPLIT of them as shares.  LH_F_P2_TASKS: every read with a call as shares, up to LH_P2_SPLIT lanes
+// scanning and probing a read's calls themselves (k_p2_tasks; pass 2 45 -> 31 ms on the repeat input, but 4.7 -> 5.4 ms on unique sequence).  LH_F_P2_SCAN: the
+// sequence before the probe kernel — the state machine over every read, or k_p2_tasks after a repeat-rich batch (the wave-chained reads of the context's PREVIOUS
+// batch, the sign K4 chooses its path by).  (A list needs N < 2^27 and the call entry's four bits of min_intv.)
+// Pass 3 in lockstep is the last to touch a read's regular slots and walks them anyway: it counts the read's seeds and lists the few reads that need their
+// intervals sorted in memory (k_smem_fin); K2 ranks the others' inside its groups.  Every other path — no pass 3, the state machine's, the lane-per-seed
+// K2, the trace build — keeps k_smem_fin over all reads.
+// The default, where the probe and the counting pass 3 both run: ONE lockstep kernel behind pass 1 does the probe's work and pass 3's (k_p23_lock: one scan
+// of the pass-1 intervals serves both; pass 3's walks need nothing of pass 2), pass 2 then appends behind pass 3's intervals and adds its own counts, and
+// k_p2_close ends it.  The bracket "k_smem4_p3" then comes FIRST and holds k_p23_lock — the probe's time with it — and "k_smem4_p2" holds pass 2 and k_p2_close.
+// LH_F_P3_LAST keeps the separate sequence: probe, pass 2, clamp, pass 3.
+struct K1Tail {
+    bool probe;       // k_p2_probe's list (or, fused, k_p23_lock's)
+    bool tasks;       // k_p2_tasks' list
+    bool list;        // pass 2 runs over one of the two
+    bool p3_lock;     // forward-only walks: one thread per read, in lockstep
+    bool p3_counts;   // ... which counts the seeds and lists the reads for k_smem_fin
+    bool fused;       // k_p23_lock, pass 2, k_p2_close
+};
+static K1Tail k1_tail_plan(const lh_context* c, const DOpts& o, int N, bool packed_reads) {
+    K1Tail t;
+    const bool list_ok = N < (1 << 27);
+    t.probe = list_ok && !(c->flags & (LH_F_P2_TASKS | LH_F_P2_SCAN)) && o.split_width < LH_P2_MAX_MIN_INTV;
+    t.p3_lock = o.max_mem_intv > 0 && packed_reads;
+    t.p3_counts = t.p3_lock && !(c->flags & LH_F_SEED_LANE);
+#ifdef LH_K1_TRACE   // (the trace build's list-length histograms are the state machine's, and its k_smem_fin runs over all reads)
+    t.probe = t.p3_counts = false;
+#endif
+    t.tasks = list_ok && !t.probe && ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek->prev_wave_reads >= ext_long_min(N)));
+    t.list = t.probe || t.tasks;
+    t.fused = t.probe && t.p3_counts && !(c->flags & LH_F_P3_LAST);
+    return t;
+}
 static int run_front(lh_context* c, const DOpts& o, int& t) {
     int N = c->b.n_reads;
     const DIndex& ix = c->idx->d;
@@ -562,34 +597,11 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
 #ifdef LH_K1_TRACE
         { int rc = k1_trace_replay(c, trace, N, g4); if (rc) return rc; }
 #endif
-        // Pass 2 runs over a list (k_smem4.h: P2TASK).  By default k_p2_probe makes it: every re-seeding call judged in lockstep, the calls that can contribute listed one
-        // by one with the probe's answer, a read with more than LH_P2_SPLIT of them as shares.  LH_F_P2_TASKS: every read with a call as shares, up to LH_P2_SPLIT lanes
-        // scanning and probing a read's calls themselves (k_p2_tasks; pass 2 45 -> 31 ms on the repeat input, but 4.7 -> 5.4 ms on unique sequence).  LH_F_P2_SCAN: the
-        // sequence before the probe kernel — the state machine over every read, or k_p2_tasks after a repeat-rich batch (the wave-chained reads of the context's PREVIOUS
-        // batch, the sign K4 chooses its path by).  A choice of path and never of result.  (A list needs N < 2^27 and the call entry's four bits of min_intv.)
         HIPCHK(hipMemsetAsync(c->d_p2_calls, 0, sizeof(P2Calls) * LH_CTR_SLOTS, c->stream));
-        const bool p2_list_ok = N < (1 << 27);
-        bool p2_probe = p2_list_ok && !(c->flags & (LH_F_P2_TASKS | LH_F_P2_SCAN)) && o.split_width < LH_P2_MAX_MIN_INTV;
-#ifdef LH_K1_TRACE
-        p2_probe = false;   // (the trace build's list-length histograms are the state machine's)
-#endif
-        const bool p2_tasks = p2_list_ok && !p2_probe && ((c->flags & LH_F_P2_TASKS) || (c->ext_hint_valid && c->h_peek->prev_wave_reads >= ext_long_min(N)));
-        // pass 3 in lockstep is the last to touch a read's regular slots and walks them anyway: it counts the read's seeds and lists the few reads that need their
-        // intervals sorted in memory (k_smem_fin below); K2 ranks the others' inside its groups.  Every other path — no pass 3, the state machine's, the lane-per-seed
-        // K2, the trace build — keeps k_smem_fin over all reads
-        const bool p3_lock = o.max_mem_intv > 0 && q4;   // forward-only walks: one thread per read, in lockstep
-        bool p3_counts = p3_lock && !(c->flags & LH_F_SEED_LANE);
-#ifdef LH_K1_TRACE
-        p3_counts = false;
-#endif
-        // The default, where the probe kernel and the counting pass 3 both run: ONE lockstep kernel behind pass 1 does the probe's work and pass 3's (k_p23_lock: one scan
-        // of the pass-1 intervals serves both; pass 3's walks need nothing of pass 2), pass 2 then appends behind pass 3's intervals and adds its own counts, and
-        // k_p2_close ends it.  The bracket "k_smem4_p3" then comes FIRST and holds k_p23_lock — the probe's time with it — and "k_smem4_p2" holds pass 2 and k_p2_close.
-        // LH_F_P3_LAST keeps the sequence below: probe, pass 2, clamp, pass 3.
-        const bool p23 = p2_probe && p3_counts && !(c->flags & LH_F_P3_LAST);
+        const K1Tail tail = k1_tail_plan(c, o, N, q4 != nullptr);
         K1Big p2 = nobig;
-        if (p2_probe || p2_tasks) { p2.list = (const int32_t*)c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo; }   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
-        if (p23) {
+        if (tail.list) { p2.list = (const int32_t*)c->d_p2_tasks; p2.count = &c->d_next_read->n_p2_tasks; p2.slot = c->d_k1_todo; }   // (slot: the reads' numbers of pass-1 intervals; pass 1's to-do list is spent)
+        if (tail.fused) {
             T_BEGIN("k_smem4_p3");
             LH_LAUNCH(k_p23_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, (const uint8_t*)c->b.seq, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_ctr, c->d_seed_cnt, c->d_p2_tasks,
                       &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
@@ -613,22 +625,22 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
 #endif
         } else {
             T_BEGIN("k_smem4_p2");
-            if (p2_probe)
+            if (tail.probe)
                 LH_LAUNCH(k_p2_probe, (N + 255) / 256, 256, c->stream, ix4, o, N, (const uint8_t*)c->b.seq, (const i64*)c->b.seq_off, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks,
                           &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
-            else if (p2_tasks)
+            else if (tail.tasks)
                 LH_LAUNCH(k_p2_tasks, (N + 255) / 256, 256, c->stream, o, N, (const DIntv*)c->d_intv, (const int32_t*)c->d_n_intv, c->d_p2_tasks, &c->d_next_read->n_p2_tasks, c->d_k1_todo, c->d_p2_calls);
             if (qw_small) smem_pass<2, false, LH_K1_QW_SMALL>(c, ix4, o, N, g4, p2);
             else smem_pass<2, false>(c, ix4, o, N, g4, p2);
-            if (p2_probe || p2_tasks) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
+            if (tail.list) LH_LAUNCH(k_p2_clamp, (N + 255) / 256, 256, c->stream, N, c->d_n_intv);
             T_END();
 #ifdef LH_K1_TRACE
             { int rc = k1_trace_lens(c, trace); if (rc) return rc; }
 #endif
             T_BEGIN("k_smem4_p3");
-            if (p3_lock)
+            if (tail.p3_lock)
                 LH_LAUNCH(k_smem_p3_lock, (N + 255) / 256, 256, c->stream, ix4, o, N, q4, (const i64*)c->b.seq_off, c->d_intv, c->d_n_intv, c->d_status, c->d_ctr,
-                          p3_counts ? c->d_seed_cnt : nullptr, p3_counts ? c->d_l_rep : nullptr, p3_counts ? c->d_fin_list : nullptr, p3_counts ? &c->d_next_read->n_fin : nullptr);
+                          tail.p3_counts ? c->d_seed_cnt : nullptr, tail.p3_counts ? c->d_l_rep : nullptr, tail.p3_counts ? c->d_fin_list : nullptr, tail.p3_counts ? &c->d_next_read->n_fin : nullptr);
             else if (o.max_mem_intv > 0)
                 smem_pass<3, false>(c, ix4, o, N, g3, nobig);
             T_END();
@@ -636,7 +648,7 @@ static int run_front(lh_context* c, const DOpts& o, int& t) {
         T_BEGIN("k_smem_fin");
         // reads whose intervals outgrew their LH_MAX_INTV slots: the three passes again into the big slab (BWA's vectors grow: no read is refused)
         { int rc = k1_big_round(c, o, ix4, N, 0); if (rc) return rc; }
-        { int rc = smem_fin(c, o, N, p3_counts); if (rc) return rc; }
+        { int rc = smem_fin(c, o, N, tail.p3_counts); if (rc) return rc; }
         T_END();
     }
     T_BEGIN("k_scan_seeds");
