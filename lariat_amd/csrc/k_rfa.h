@@ -328,6 +328,89 @@ __device__ __forceinline__ double dev_fast_score_w(const DCand& R, const DInf& S
     return change;
 }
 
+// (r17) fastScore of one source against ALL sinks of a barcode of at most 32 molecules, several lanes per sink (the small instance).  One lane per sink left 4-10 of
+// the 64 lanes walking the source's alignments four at a time, a table read and the gather it names per step: seven steps in a row for a molecule of 28.  Here sink i
+// has the G = 64 / (M rounded up to a power of two, at least 2) contiguous lanes [i * G, i * G + G): in one step they read the table entries of G * 4 consecutive
+// alignments of the source — sub-lane j those at s0 + u * G + j, u = 0..3 — and then the log probabilities those name, all before a sum is touched.  Every sub-lane of
+// the sink then walks the step's alignments in the map's order and takes each term from the sub-lane that read it (a cross-lane move; which alignments count, and
+// with which pair term, from ballots): the additions per sink are the ones dev_fast_score_w makes, in its order, and all sub-lanes of a sink end with the same sums.
+// The source is at most LH_RFA_SRC_CHUNK alignments (the caller's condition).  *snk_out: the lane's sink or -1 (the source itself, or beyond M); *own_out: the molecule whose first lane this is, or -1.
+template <typename HOT>
+__device__ __forceinline__ double dev_fast_score_spread(const DCand& R, const DInf& S, const RfaTab& T, const HOT& H, i64 c_lo, int r0, int M, int src, double lup,
+                                                        int32_t* sLr, int32_t* sFl, double* sLap, int* num_out, int* snk_out, int* own_out) {
+    const int lane = LANE();
+    int lg = 5;   // log2 of G
+    while (lg > 1 && (64 >> lg) < M) --lg;
+    const int G = 1 << lg, sub = lane & (G - 1), base = lane - sub, si = lane >> lg;
+    const int snk = (si < M && si != src) ? si : -1;
+    const uint32_t gmask = 0xffffffffu >> (32 - G);
+    const int n = H.alen[src];
+    int num = 0;
+    dev_fast_score_w(R, S, T, H, c_lo, r0, M, src, -1, lup, sLr, sFl, sLap, &num, 0, (int*)0);   // stages the source (a call with idle lanes)
+#ifdef LH_RFA_SPREAD_WEAK
+    const int cn = n - n % (4 * G);   // (test build, never shipped: the last partial step of a source is left out)
+#else
+    const int cn = n;
+#endif
+    double change = 0, alignment_change = 0;
+    for (int s0 = 0; s0 < cn; s0 += 4 * G) {
+        int tq4[4];
+        double d4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int s = s0 + u * G + sub;
+            tq4[u] = snk >= 0 && s < cn ? T.bestT[(size_t)sLr[s] * M + snk] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) d4[u] = tq4[u] >= 0 ? R.lap[c_lo + (tq4[u] & RFA_T_MASK)] : 0.0;
+        int pk = 0;   // per alignment of the lane: bit 2 it counts, bits 0-1 its pair term (1: +lup/2, 2: -lup/2)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int tq = tq4[u], s = s0 + u * G + sub;
+            if (tq >= 0) {
+                int fl = sFl[s];
+                int hm = fl & 1, hp = fl >> 1;
+                int skp = (tq & RFA_T_PAIR) && hm;                    // sink_has_mate_pair
+                pk |= (4 | (hp && !skp ? 1 : (!hp && skp ? 2 : 0))) << (4 * u);
+                d4[u] = d4[u] - sLap[s];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int pu = pk >> (4 * u);
+            const u64 mv = __ballot(pu & 4);
+            if (!mv) continue;   // (most reads have no alignment in most sinks)
+            const u64 mpl = __ballot((pu & 3) == 1), mmi = __ballot((pu & 3) == 2);
+            const uint32_t gv = (uint32_t)(mv >> base) & gmask, gp = (uint32_t)(mpl >> base) & gmask, gn = (uint32_t)(mmi >> base) & gmask;
+            u64 any = mv;
+            for (int w = G; w < 64; w <<= 1) any |= any >> w;
+            for (uint32_t js = (uint32_t)any & gmask; js; js &= js - 1) {   // the sub-lanes that hold a term of some sink, in the map's order
+                const int j = __builtin_ctz(js);
+                const double d = __shfl(d4[u], base + j);
+                if (gv >> j & 1) {
+                    alignment_change += d;
+                    if (gp >> j & 1) alignment_change += lup / 2.0;
+                    else if (gn >> j & 1) alignment_change -= lup / 2.0;
+                    num++;
+                }
+            }
+        }
+    }
+    if (snk >= 0) {
+        int sb = dev_mol_active(H.alen[src], H.nbest[src], 0), sa = dev_mol_active(H.alen[src], H.nbest[src], -num);
+        if (!sa && sb) change -= (double)H.nbest[src] * -0.5;
+        int kb = dev_mol_active(H.alen[snk], H.nbest[snk], 0), ka = dev_mol_active(H.alen[snk], H.nbest[snk], num);
+        if (ka && !kb) change += (double)H.nbest[snk] * -0.5;
+        if (H.alen[src] - num == 0 && num > 0) change -= -3.0;
+        if (H.alen[snk] == 0 && num > 0) change += -3.0;
+        change += alignment_change;
+    }
+    *num_out = num;
+    *snk_out = snk;
+    if (own_out) *own_out = sub == 0 && si < M ? si : -1;
+    return change;
+}
+
 __device__ __forceinline__ u64 dev_mix64(u64 x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
     return x;
@@ -1363,14 +1446,23 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 if (H.alen[source] == 0) { source = (source + 1) % M; continue; }
                 double bs = -1.7976931348623157e308;
                 int bl = -1, bi = 0x7fffffff;
+                int staged = 0;
+                if (SMALL && M <= 32) {   // (the small instance) several lanes per sink: the reduction below sees a sink more than once, with the same values
+                    if constexpr (SMALL) {
+                        int num, snk;
+                        double sc = dev_fast_score_spread(R, S, T, H, c_lo, r0, M, source, improper, sLr, sFl, sLap, &num, &snk, (int*)0);
+                        if (snk >= 0 && num > 0) { bs = sc; bl = H.alen[snk]; bi = snk; }
+                    }
+                } else {
                 const u64 groups = stage_source(source);
-                const int staged = groups != ~0ull;
+                staged = groups != ~0ull;
                 for (int sb = 0; sb < M; sb += 64) {
                     if (!(groups >> ((sb >> 6) & 63) & 1)) continue;   // (no sink here has a read of the source to move: num = 0 for all of them)
                     int i = sb + lane, num;
                     int snk = (i < M && i != source) ? i : -1;
                     double sc = dev_fast_score_w(R, S, T, H, c_lo, r0, M, source, snk, improper, sLr, sFl, sLap, &num, 0, (int*)0, staged);
                     if (snk >= 0 && num > 0 && (sc > bs || (sc == bs && H.alen[i] > bl))) { bs = sc; bl = H.alen[i]; bi = i; }
+                }
                 }
                 for (int msk = 32; msk >= 1; msk >>= 1) {   // lexicographic max of (score, sink size), first index on full ties
                     double os = __shfl_xor(bs, msk);
@@ -1408,6 +1500,14 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             RFA_FENCE()
             // ---- moleculeMapqProbabilitySums ----
             for (int s = 0; s < M; ++s) {
+                if (SMALL && M <= 32) {   // (the small instance) several lanes per sink, the first of them writes P[t]
+                    if constexpr (SMALL) {
+                        int num, snk, t;
+                        double sc = dev_fast_score_spread(R, S, T, H, c_lo, r0, M, s, improper, sLr, sFl, sLap, &num, &snk, &t);
+                        const double pv = pow(10.0, sc);
+                        if (t >= 0) H.P[t] = t == s ? 0.0 : pv;
+                    }
+                } else {
                 const u64 groups = stage_source(s);
                 const int staged = groups != ~0ull;
                 for (int sb = 0; sb < M; sb += 64) {
@@ -1415,6 +1515,7 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                     int t = sb + lane, num;
                     double sc = dev_fast_score_w(R, S, T, H, c_lo, r0, M, s, (t < M && t != s) ? t : -1, improper, sLr, sFl, sLap, &num, 0, (int*)0, staged);
                     if (t < M) H.P[t] = t == s ? 0.0 : pow(10.0, sc);
+                }
                 }
                 WAVE_SYNC();
                 RFA_PROF(8)
@@ -1439,6 +1540,41 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
             RFA_PROF(8)
             RFA_FENCE()
             // ---- updateAlignmentsMoleculeStatus: confidences, differences, active molecules ----
+            if constexpr (SMALL) {
+                // (r17) the lanes share a molecule's alignments: 64 / (M rounded up to a power of two) contiguous lanes per molecule, 64 molecules at a time, four
+                // alignments a lane in flight.  A lane per molecule read the two columns of its ~28 alignments one after the other, a tenth of the wave at work; the
+                // sums are integers, exact in any order.
+                int lgm = 6;
+                while (lgm > 0 && (64 >> lgm) < M) --lgm;
+                const int Gm = 1 << lgm, sub = lane & (Gm - 1);
+                for (int mb = 0; mb < M; mb += 64 >> lgm) {
+                    const int m = mb + (lane >> lgm);
+                    const int al = m < M ? H.alen[m] : 0, ao = m < M ? H.aoff[m] : 0;
+                    int soft = 0, diffs = 0;
+                    for (int k = sub; k < al; k += 4 * Gm) {
+                        int a4[4], sc4[4], mm4[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) a4[u] = k + u * Gm < al ? H.act_store[ao + k + u * Gm] : -1;
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            sc4[u] = a4[u] >= 0 ? R.soft_clipped[c_lo + a4[u]] : 0;
+                            mm4[u] = a4[u] >= 0 ? R.mismatches[c_lo + a4[u]] : 0;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) { soft += sc4[u] > 0; diffs += mm4[u]; }
+                    }
+                    for (int msk = Gm >> 1; msk >= 1; msk >>= 1) { soft += __shfl_xor(soft, msk); diffs += __shfl_xor(diffs, msk); }
+                    if (m < M) {
+                        double conf = (double)al / (double)H.nbest[m];
+                        double diff = (double)diffs / (double)al;
+                        for (int k = sub; k < al; k += Gm) {
+                            int a = H.act_store[ao + k];
+                            S.mol_conf[c_lo + a] = conf; S.mol_diff[c_lo + a] = diff;
+                        }
+                        if (sub == 0) H.mflag[m] = (al - soft > 4 && conf > 0.1) ? 1 : 0;
+                    }
+                }
+            } else
             for (int m = lane; m < M; m += 64) {
                 double conf = (double)H.alen[m] / (double)H.nbest[m];
                 int soft = 0, diffs = 0;
