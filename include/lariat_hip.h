@@ -551,6 +551,18 @@ int lh_bam_set_device_records(lh_bam_writer* w, int32_t on);
 /* the last append on that path: host gather, upload, plan kernels (offsets included), write kernel, in seconds.  lh_bam_timings then reports records_s = their
  * sum, join_s = 0, write_s = compression + download + fwrite */
 int lh_bam_records_timings(const lh_bam_writer* w, double out[4]);
+/* lh_bam_append with the batch's result read where lh_align_resident left it: no lh_result_download, no host copy of the result.
+ * w has a compressor and device records set; ctx holds the result of its last lh_align_resident, run whole (one round) with inference, on the compressor's device;
+ * `in` is the ingest batch those reads came from.  The files are those of lh_result_download + lh_bam_append, byte for byte.  Two kernels (k_brec_gather_count,
+ * k_brec_gather_fill) gather the at most four candidates a read's records read straight from the context's arrays, every lane's part of a context with lanes > 1 at
+ * its reads; the context's result stays as it is and may still be downloaded.  lh_bam_records_timings' out[0] is then the gather kernels' time, out[1] the upload of
+ * the batch's text alone.  LH_E_ARG, with nothing appended and the writer going on: no compressor or no device records, LH_REC_DEBUG_TAGS, nothing aligned yet, the
+ * last align ran without inference, `in` is not the selected batch, compressor and context on different devices, a read without an active alignment, or a batch that
+ * was aligned in rounds: its result was merged on the host already, lh_result_download + lh_bam_append cost nothing extra there.  What lh_result_download refuses
+ * (a per-read limit, a workspace overflow, a watchdog word) is refused here with the same code and nothing is appended.  An ingest batch without pairs (the end of
+ * the input) reads nothing of ctx.  Another thread's lh_align_resident or lh_stage_dump_resident on ctx waits until the gather kernels have read the result; uploads and selects are the
+ * caller's to keep off the context during the call. */
+int lh_bam_append_resident(lh_bam_writer* w, lh_context* ctx, const lh_ingest_batch* in);
 /* diagnostics: the device's printf("%.6f") (k_brec.h; the DM tag), n values -> 32 bytes each, NUL-terminated.  Exact for every finite |v| < 2^31: correctly rounded from
  * the binary value, ties to even, as glibc prints.  Any other value: its 32 bytes are zero and the call returns LH_E_LIMIT.  LH_E_NODEVICE without a GPU. */
 int lh_diag_format_f6(int device, int32_t n, const double* v, char* out /* 32 bytes per value, NUL-terminated */);

@@ -992,6 +992,13 @@ class BamWriter:
         rs = result.as_struct()
         self.lib.check(self.lib.L.lh_bam_append(self.h, C.byref(rs), ingest_batch.ptr))
 
+    def append_resident(self, ctx, ingest_batch):
+        """lh_bam_append_resident: the records of the batch `ctx` aligned last, gathered on the device from the context's resident result (no download);
+        needs set_device and set_device_records"""
+        self.lib.L.lh_bam_append_resident.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LhIngestBatch)]
+        self.lib.L.lh_bam_append_resident.restype = C.c_int
+        self.lib.check(self.lib.L.lh_bam_append_resident(self.h, ctx.h if ctx is not None else None, ingest_batch.ptr if ingest_batch is not None else None))
+
     def close(self):
         if self.h:
             h, self.h = self.h, None
@@ -1048,4 +1055,5 @@ EXPORTED_SYMBOLS = [
     "lh_index_opts_init", "lh_context_opts_init", "lh_index_build_device", "lh_index_export", "lh_index_save", "lh_synth_genome", "lh_synth_reads", "lh_synth_write_fastq9", "lh_diag_index_check", "lh_batch_upload_slot", "lh_batch_select", "lh_bam_concat", "lh_reference_pack", "lh_index_set_holes", "lh_diag_index_digest", "lh_index_set_alt", "lh_index_alt", "lh_bam_set_level", "lh_bam_timings", "lh_result_download_begin", "lh_result_download_end", "lh_batch_stage_slot", "lh_host_alloc", "lh_host_free",
     "lh_bgzf_create", "lh_bgzf_free", "lh_bgzf_compress", "lh_bgzf_bound", "lh_bgzf_timings", "lh_bam_set_device",
     "lh_bam_set_device_records", "lh_bam_records_timings", "lh_diag_format_f6",
+    "lh_bam_append_resident",
 ]

@@ -213,18 +213,19 @@ bool flush_device(lh_bam_writer* w, bool all) {
 }
 
 // lh_bam_append with the records made on the device (lh_bam_set_device_records): the encoder hands back every file's members and the bytes behind its last whole
-// block, which become its `pending` — the one carrier of state between appends on every path
-int append_device(lh_bam_writer* w, const lh_result* res, const lh_ingest_batch* in) {
+// block, which become its `pending` — the one carrier of state between appends on every path.  The rows the kernels read come from the downloaded result `res`, or
+// (lh_bam_append_resident) from the result resident in `ctx`
+int append_device(lh_bam_writer* w, const lh_result* res, lh_context* ctx, const lh_ingest_batch* in) {
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     if (w->rec_flags & LH_REC_DEBUG_TAGS)
         return lh_set_error_(LH_E_ARG, "lh_bam_append: the debug tags (LH_REC_DEBUG_TAGS) are a feature of the host record path: not with lh_bam_set_device_records; nothing was appended");
     const double t0 = now();
     LhBrecCall c;
-    c.res = res; c.in = in; c.names = &w->names; c.bucket = &w->bucket; c.chunk = w->chunk; c.threads = w->threads;
+    c.res = res; c.ctx = ctx; c.in = in; c.names = &w->names; c.bucket = &w->bucket; c.chunk = w->chunk; c.threads = w->threads;
     for (Out& o : w->outs) c.pending.push_back(&o.pending);
     c.zbuf = &w->zbuf; c.zbuf_cap = &w->zbuf_cap;
     const int rc = lh_brec_encode_(w->dev, &c);
-    if (rc == LH_E_LIMIT || rc == LH_E_ARG) return rc;   // the batch was turned away before a byte was written: the writer goes on
+    if (rc == LH_E_LIMIT || rc == LH_E_ARG || (rc && c.refused)) return rc;   // the batch was turned away before a byte was written: the writer goes on
     if (rc) {
         w->failed = true;
         const std::string why = std::string("lh_bam_append: encoding or compression on the device failed: ") + lh_last_error();
@@ -380,7 +381,7 @@ extern "C" int lh_bam_timings(const lh_bam_writer* w, double* records_s, double*
 }
 extern "C" int lh_bam_append(lh_bam_writer* w, const lh_result* res, const lh_ingest_batch* in) {
     if (!w || !res || !in) return lh_set_error_(LH_E_ARG, "lh_bam_append: null argument");
-    if (w->dev && w->dev_records) return append_device(w, res, in);
+    if (w->dev && w->dev_records) return append_device(w, res, nullptr, in);
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now();
     std::vector<const char*> names;
@@ -434,6 +435,14 @@ extern "C" int lh_bam_append(lh_bam_writer* w, const lh_result* res, const lh_in
     }
     w->t_records = t1 - t0; w->t_join = t3 - t2; w->t_write = now() - t3;   // lh_bam_timings
     return LH_OK;
+}
+
+extern "C" int lh_bam_append_resident(lh_bam_writer* w, lh_context* ctx, const lh_ingest_batch* in) {
+    if (!w || !ctx || !in) return lh_set_error_(LH_E_ARG, "lh_bam_append_resident: null argument");
+    if (!w->dev || !w->dev_records)
+        return lh_set_error_(LH_E_ARG, "lh_bam_append_resident: the writer needs a device compressor (lh_bam_set_device) and device records (lh_bam_set_device_records): the records are gathered and "
+                                       "encoded on the compressor's device; nothing was appended");
+    return append_device(w, nullptr, ctx, in);
 }
 
 extern "C" int lh_bam_set_flags(lh_bam_writer* w, int32_t flags) {

@@ -9,13 +9,18 @@
 //                  bucket (a stable sort by file, then a scan: records of one file keep input order, which is what the host's join gives).
 //   k_brec_write   a 16-lane group per record, one wave per pair: the lanes stride over the record's bytes and store each to both places.
 //   k_brec_f6      the %.6f of the DM tag on its own (lh_diag_format_f6).
+//   k_brec_gather_count / k_brec_gather_fill   the rows the kernels above read, gathered from a context's resident result (lh_bam_append_resident) instead of by the
+//                  host from a downloaded one: a lane per read counts its CIGAR operations and mismatch loci, two scans place them, a 16-lane group per read fills.
 #pragma once
 #include "lh_dev.h"
+#include "k_rfa.h"   // DCand (k_aln.h), DInf: where a context's result lies
 
 #define LH_BREC_SLOTS 4   // rows gathered per read: the active alignment, its split, the second best, the active's mate
 #define LH_BREC_WD_LOOP 1   // watchdog word: a loop over a CIGAR or a mismatch list ran out of its budget
 #define LH_BREC_E_FORMAT 1  // err[0] bits: a read name over 254 bytes or more than 65,535 CIGAR operations
 #define LH_BREC_E_DM 2      // ... a molecule_difference that is not finite or not below 2^31
+#define LH_BREC_E_NOACTIVE 4   // the device gather's own word: a read has no active alignment
+#define LH_BREC_E_INDEX 8      // ... a candidate index or a mismatch list's continuation lies outside the result
 // which optional tags a record has (BrecPlan::tags)
 #define LH_BREC_T_TR 1
 #define LH_BREC_T_BC 2
@@ -501,5 +506,108 @@ __global__ void __launch_bounds__(64) k_brec_write(BrecIn in, const BrecPlan* __
             for (int q = 0; q < n; ++q) brec_put(d, at + incl - n + q, b[q]);
             at += total;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the gather from a resident result
+// brec_gather (lh_brec.inc) on the device: the stage buffer's rows, doubles, packed CIGARs and packed loci come out as the host's gather and upload leave them, read
+// by read and slot by slot.  The kernels read one pipeline's DCand / DInf and write the encoder's buffers alone.
+struct BrecSrc {   // one pipeline's part of the batch
+    int32_t n_reads;   // of the part
+    i64 read0;         // its first read in the batch
+    i64 n_cand;        // cand_off[n_reads]: every index below is -1 or smaller than this
+    DCand R; DInf S;
+};
+// the candidates read r's records read (-1: none): the active alignment, its split, the second best, the active's mate.  An index outside the result counts as none
+__device__ __forceinline__ void brec_slots(const BrecSrc& s, int r, i64* idx, int32_t* __restrict__ err) {
+    idx[0] = s.S.active_idx[r]; idx[1] = s.S.split_idx[r]; idx[2] = s.S.second_best_idx[r];
+    for (int k = 0; k < 3; ++k) if (idx[k] < -1 || idx[k] >= s.n_cand) { idx[k] = -1; atomicOr(err, (int32_t)LH_BREC_E_INDEX); }
+    idx[3] = idx[0] >= 0 ? s.S.mate[idx[0]] : -1;
+    if (idx[3] < -1 || idx[3] >= s.n_cand) { idx[3] = -1; atomicOr(err, (int32_t)LH_BREC_E_INDEX); }
+}
+__device__ __forceinline__ int brec_n_cig(const BrecSrc& s, i64 a) {   // (a count over the slots has raised LH_ST_CIGAR_OVERFLOW: such a result is refused before)
+    const int n = s.R.n_cigar[a];
+    return n < 0 ? 0 : n > LH_MAX_CIGAR ? LH_MAX_CIGAR : n;
+}
+__device__ __forceinline__ int brec_n_mm(const BrecSrc& s, i64 a, int32_t* __restrict__ err) {   // loci past the slots continue in the pool: all of them inside it
+    const int n = s.R.n_mm[a];
+    if (n <= LH_MAX_MM) return n < 0 ? 0 : n;
+    const i64 xo = s.R.mm_xoff[a];
+    if (xo < 0 || xo + (n - LH_MAX_MM) > (i64)s.R.mm_xcap) { atomicOr(err, (int32_t)LH_BREC_E_INDEX); return LH_MAX_MM; }
+    return n;
+}
+
+// a lane per read: its CIGAR operations (slots 0 and 1) and mismatch loci (slots 0 to 2) at its place in the batch; the host path's "a read has no active alignment"
+__global__ void __launch_bounds__(256) k_brec_gather_count(BrecSrc s, i64* __restrict__ n_cig, i64* __restrict__ n_mm, int32_t* __restrict__ err) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= s.n_reads) return;
+    i64 idx[LH_BREC_SLOTS];
+    brec_slots(s, r, idx, err);
+    if (idx[0] < 0) { atomicOr(err, (int32_t)LH_BREC_E_NOACTIVE); atomicMin(err + 1, (int32_t)(s.read0 + r)); }
+    i64 nc = 0, nm = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (idx[k] < 0) continue;
+        if (k < 2) nc += brec_n_cig(s, idx[k]);
+        nm += brec_n_mm(s, idx[k], err);
+    }
+    n_cig[s.read0 + r] = nc; n_mm[s.read0 + r] = nm;
+}
+
+// a 16-lane group per read.  Lanes 0 to 3 write the four rows (brec_gather_row: a whole row zeroed, ci, then the fields), lanes 4 to 7 the four doubles; then the group
+// strides the read's lists.  The rows are of fixed width and the lists short (a handful of entries in the mean, 64 and the pool at most), so a read keeps a quarter
+// of a wave busy where a wave per read would idle three quarters of it, and the group's stores to a list are consecutive words.
+__global__ void __launch_bounds__(256) k_brec_gather_fill(BrecSrc s, const i64* __restrict__ cig_at, const i64* __restrict__ mm_at, BrecRow* __restrict__ row, double* __restrict__ rd,
+                                                          uint32_t* __restrict__ cig, int32_t* __restrict__ mm, int32_t* __restrict__ err, int32_t* wd) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = (int)(t >> 4), sub = (int)(t & 15);
+    if (r >= s.n_reads) return;
+    const i64 read = s.read0 + r;
+    i64 idx[LH_BREC_SLOTS];
+    brec_slots(s, r, idx, err);
+    int nc[2], nm[3];
+    for (int k = 0; k < 3; ++k) {
+        if (k < 2) nc[k] = idx[k] < 0 ? 0 : brec_n_cig(s, idx[k]);
+        nm[k] = idx[k] < 0 ? 0 : brec_n_mm(s, idx[k], err);
+    }
+    const i64 c0 = cig_at[read], m0 = mm_at[read];
+    if (sub < LH_BREC_SLOTS) {
+        const i64 a = idx[sub];
+        BrecRow o;
+        __builtin_memset(&o, 0, sizeof o);
+        o.ci = a;
+        if (a >= 0) {
+            o.pos = s.R.pos[a]; o.aend = s.R.aend[a]; o.rid = s.R.rid[a]; o.score = s.R.score[a]; o.mapq = s.S.mapq[a]; o.mol_id = s.S.molecule_id[a];
+            o.mol_diff = s.S.mol_diff[a];
+            o.reversed = s.R.reversed[a]; o.is_proper = s.S.is_proper[a]; o.duplicate = s.S.duplicate[a]; o.active_mol = s.S.active_molecule[a];
+            if (sub < 2) { o.cig_off = c0 + (sub ? nc[0] : 0); o.n_cig = nc[sub]; }
+            if (sub < 3) { o.mm_off = m0 + (sub > 0 ? nm[0] : 0) + (sub > 1 ? nm[1] : 0); o.n_mm = nm[sub]; }
+        }
+        row[read * LH_BREC_SLOTS + sub] = o;
+    } else if (sub < 8) {
+        const double* __restrict__ src = sub == 4 ? s.S.second_best_score : sub == 5 ? s.S.as_score : sub == 6 ? s.S.split_second_best : s.S.split_score;
+        rd[read * 4 + (sub - 4)] = src[r];
+    }
+    int budget = 1 << 12;   // (a list is at most a read's bases long, a sixteenth of it per lane)
+    i64 c_at = c0, m_at = m0;
+    for (int k = 0; k < 3; ++k) {
+        const i64 a = idx[k];
+        if (a < 0) continue;
+        if (k < 2) {
+            const uint32_t* __restrict__ src = s.R.cigar + a * LH_MAX_CIGAR;
+            for (int j = sub; j < nc[k]; j += 16) {
+                LH_WATCH(wd, budget, LH_BREC_WD_LOOP, break)
+                cig[c_at + j] = src[j];
+            }
+            c_at += nc[k];
+        }
+        const int32_t* __restrict__ ref = s.R.mm_ref + a * LH_MAX_MM;
+        const int32_t* __restrict__ rdl = s.R.mm_read + a * LH_MAX_MM;
+        const i64 xo = nm[k] > LH_MAX_MM ? (i64)s.R.mm_xoff[a] - LH_MAX_MM : 0;   // locus j >= LH_MAX_MM is entry mm_xoff[a] + j - LH_MAX_MM of the pool (k_pack_slots)
+        for (int j = sub; j < nm[k]; j += 16) {
+            LH_WATCH(wd, budget, LH_BREC_WD_LOOP, break)
+            mm[2 * (m_at + j)] = j < LH_MAX_MM ? ref[j] : s.R.mm_xref[xo + j];
+            mm[2 * (m_at + j) + 1] = j < LH_MAX_MM ? rdl[j] : s.R.mm_xread[xo + j];
+        }
+        m_at += nm[k];
     }
 }

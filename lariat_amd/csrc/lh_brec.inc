@@ -6,6 +6,8 @@
 // the ingest batch's text as it is; k_brec_plan sizes every record; the offsets (rocPRIM's radix sort by file and two scans; std::stable_sort under the emulator) give
 // every record its place in bc_sorted and in its bucket file; k_brec_write stores the bytes behind each file's `pending` bytes in one device buffer, a region per file;
 // k_bgzf compresses every whole block of every region from there.  Only the members and each file's last partial block come back.
+// One lh_bam_append_resident: the same, but the staging buffer's contents are produced on the device, by k_brec_gather_count, two scans and k_brec_gather_fill from
+// the arrays lh_align_resident left in the context; the result is not downloaded, and everything behind the staging buffer is shared.
 #include "k_brec.h"
 #include "brec_internal.h"
 #include <chrono>
@@ -16,7 +18,7 @@ struct lh_brec_bufs {
     Dev text, stage, plan, work, tmp, out;
     void* h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked: the gathered rows
     i64* h_small = nullptr; size_t h_small_cap = 0;    // page-locked: what comes back between the offsets and the write (file_end, the total, err, watchdog)
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // upload begins / ends, plan begins, offsets end, write begins / ends
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // upload begins / ends, plan begins, offsets end, write begins / ends, the device gather begins / ends
 };
 static void brec_free(lh_brec_bufs* b) {
     if (!b) return;
@@ -105,7 +107,9 @@ void brec_gather(const lh_result* r, i64 r0, i64 r1, BrecRow* rows, double* rd, 
     }
 }
 
-int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
+// srcs == null: the stage buffer comes from c->res by the host's gather and one upload.  Else the device gathers it from the pipelines' resident results (`srcs`, a part
+// of the batch each); ctx_lock holds the context's mutex and is released once the gather kernels have completed
+int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B, const std::vector<BrecSrc>* srcs, std::unique_lock<std::mutex>* ctx_lock) {
     const lh_result* res = c->res;
     const lh_ingest_batch* in = c->in;
     const i64 n_pairs = in->batch.n_pairs, n_reads = 2 * n_pairs, n_slots = 4 * n_pairs;
@@ -119,31 +123,96 @@ int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
     i64 total = 0;
     z->t_up = z->t_kernel = z->t_down = 0;
     if (n_pairs > 0) {
-        // ---- 1. gather: counts, then the rows, by ranges of reads
-        const double tg0 = brec_now();
-        int nt = c->threads < 1 ? 1 : c->threads;
-        if ((i64)nt > (n_pairs + 255) / 256) nt = (int)((n_pairs + 255) / 256);
-        std::vector<i64> cig_at((size_t)nt + 1, 0), mm_at((size_t)nt + 1, 0);
-        auto each = [&](const std::function<void(int)>& f) {
-            std::vector<std::thread> th;
-            for (int t = 1; t < nt; ++t) th.emplace_back(f, t);
-            f(0);
-            for (auto& t : th) t.join();
-        };
-        each([&](int t) { i64 ca = 0, ma = 0; brec_gather(res, n_reads * t / nt, n_reads * (t + 1) / nt, nullptr, nullptr, nullptr, nullptr, ca, ma); cig_at[(size_t)t + 1] = ca; mm_at[(size_t)t + 1] = ma; });
-        for (int t = 0; t < nt; ++t) { cig_at[(size_t)t + 1] += cig_at[(size_t)t]; mm_at[(size_t)t + 1] += mm_at[(size_t)t]; }
+        // the work buffer's sections (laid out first: the device gather keeps its counts and scans there)
+        BrecLayout wl;
+        const size_t N = (size_t)n_slots;
+        const size_t w_key0 = wl.add(N * 4), w_key1 = wl.add(N * 4), w_val0 = wl.add(N * 4), w_val1 = wl.add(N * 4);
+        const size_t w_sz = wl.add((N + 1) * 8), w_offbc = wl.add((N + 1) * 8), w_ssz = wl.add((N + 1) * 8), w_sscan = wl.add((N + 1) * 8), w_offf = wl.add(N * 8);
+        const size_t w_fend = wl.add((size_t)n_out * 8), w_fbase = wl.add((size_t)n_out * 8), w_err = wl.add(16), w_wd = wl.add(LH_WD_SLOTS * 4);
+        const size_t R1 = srcs ? (size_t)n_reads + 1 : 0;   // the device gather's: per read the CIGAR operations and loci, their scans, its error and watchdog words
+        const size_t w_gnc = wl.add(R1 * 8), w_gnm = wl.add(R1 * 8), w_gcs = wl.add(R1 * 8), w_gms = wl.add(R1 * 8), w_gerr = wl.add(srcs ? 16 + LH_WD_SLOTS * 4 : 0);
+        const size_t small_words = (size_t)n_out + 1 + 2 + LH_WD_SLOTS / 2, small_gather = 2 + LH_WD_SLOTS / 2;   // (page-locked words; the gather's behind the others)
         BrecLayout sl;
-        const size_t s_row = sl.add((size_t)n_reads * LH_BREC_SLOTS * sizeof(BrecRow)), s_rd = sl.add((size_t)n_reads * 4 * sizeof(double));
-        const size_t s_cig = sl.add((size_t)cig_at[(size_t)nt] * 4), s_mm = sl.add((size_t)mm_at[(size_t)nt] * 8);
-        int rc = brec_pinned(&B->h_stage, &B->h_stage_cap, sl.total);
-        if (!rc) rc = brec_dev(B->stage, sl.total);
-        if (rc) return rc;
-        uint8_t* hs = (uint8_t*)B->h_stage;
-        each([&](int t) {
-            i64 ca = cig_at[(size_t)t], ma = mm_at[(size_t)t];
-            brec_gather(res, n_reads * t / nt, n_reads * (t + 1) / nt, (BrecRow*)(hs + s_row), (double*)(hs + s_rd), (uint32_t*)(hs + s_cig), (int32_t*)(hs + s_mm), ca, ma);
-        });
-        c->t[0] = brec_now() - tg0;
+        size_t s_row = 0, s_rd = 0, s_cig = 0, s_mm = 0;
+        uint8_t* hs = nullptr;
+        int rc = LH_OK;
+        if (srcs) {
+            // ---- 1. gather on the device, from the context's arrays: counts per read, two scans (read order, then slot order: the order the host's threads produce), fill
+            rc = brec_dev(B->work, wl.total);
+            if (!rc) rc = brec_pinned((void**)&B->h_small, &B->h_small_cap, (small_words + small_gather) * 8);
+            size_t g_tmp = 16;
+#ifndef LH_EMU
+            { size_t b = 0; HIPCHK(rocprim::exclusive_scan(nullptr, b, (const i64*)nullptr, (i64*)nullptr, (i64)0, R1, rocprim::plus<i64>(), st)); g_tmp = b + 16; }
+#endif
+            if (!rc) rc = brec_dev(B->tmp, g_tmp);
+            if (rc) return rc;
+            uint8_t* gw = (uint8_t*)B->work.p;
+            i64 *g_nc = (i64*)(gw + w_gnc), *g_nm = (i64*)(gw + w_gnm), *g_cs = (i64*)(gw + w_gcs), *g_ms = (i64*)(gw + w_gms);
+            int32_t *g_err = (int32_t*)(gw + w_gerr), *g_wd = g_err + 4;
+            HIPCHK(hipEventRecord(B->ev[6], st));
+            HIPCHK(hipMemsetAsync(g_nc, 0, R1 * 8, st));   // (entry n_reads stays 0: the scan's last element is then the total)
+            HIPCHK(hipMemsetAsync(g_nm, 0, R1 * 8, st));
+            HIPCHK(hipMemsetAsync(g_err, 0, 16 + LH_WD_SLOTS * 4, st));
+            const int32_t g_err_init[4] = {0, 0x7fffffff, 0, 0};
+            HIPCHK(hipMemcpyAsync(g_err, g_err_init, 16, hipMemcpyHostToDevice, st));
+            for (const BrecSrc& s : *srcs) if (s.n_reads > 0) LH_LAUNCH(k_brec_gather_count, (s.n_reads + 255) / 256, 256, st, s, g_nc, g_nm, g_err);
+            HIPCHK(hipGetLastError());
+#ifdef LH_EMU
+            { i64 rc_ = 0, rm_ = 0; for (size_t i = 0; i < R1; ++i) { g_cs[i] = rc_; rc_ += g_nc[i]; g_ms[i] = rm_; rm_ += g_nm[i]; } }
+#else
+            {
+                size_t tb = B->tmp.cap;
+                HIPCHK(rocprim::exclusive_scan(B->tmp.p, tb, (const i64*)g_nc, g_cs, (i64)0, R1, rocprim::plus<i64>(), st));
+                tb = B->tmp.cap;
+                HIPCHK(rocprim::exclusive_scan(B->tmp.p, tb, (const i64*)g_nm, g_ms, (i64)0, R1, rocprim::plus<i64>(), st));
+            }
+#endif
+            i64* gh = B->h_small;   // the two totals, the error words
+            HIPCHK(hipMemcpyAsync(gh, g_cs + n_reads, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(gh + 1, g_ms + n_reads, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(gh + 2, g_err, 16, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            const int32_t* gh_err = (const int32_t*)(gh + 2);
+            if (gh_err[0] & LH_BREC_E_INDEX) return set_err(LH_E_HIP, "lh_bam_append_resident: the context's result holds a candidate index or a mismatch list outside its arrays; nothing was appended");
+            if (gh_err[0] & LH_BREC_E_NOACTIVE) return set_err(LH_E_ARG, "lh_bam_append_resident: a read has no active alignment (read " + std::to_string(gh_err[1]) + "); nothing was appended");
+            if (gh[0] < 0 || gh[1] < 0) return set_err(LH_E_HIP, "lh_bam_append_resident: the gather's totals are negative");
+            s_row = sl.add((size_t)n_reads * LH_BREC_SLOTS * sizeof(BrecRow)); s_rd = sl.add((size_t)n_reads * 4 * sizeof(double));
+            s_cig = sl.add((size_t)gh[0] * 4); s_mm = sl.add((size_t)gh[1] * 8);
+            rc = brec_dev(B->stage, sl.total);
+            if (rc) return rc;
+            uint8_t* gs = (uint8_t*)B->stage.p;
+            for (const BrecSrc& s : *srcs)
+                if (s.n_reads > 0)
+                    LH_LAUNCH(k_brec_gather_fill, (int)(((i64)s.n_reads * 16 + 255) / 256), 256, st, s, (const i64*)g_cs, (const i64*)g_ms, (BrecRow*)(gs + s_row), (double*)(gs + s_rd), (uint32_t*)(gs + s_cig),
+                              (int32_t*)(gs + s_mm), g_err, g_wd);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(B->ev[7], st));
+        } else {
+            // ---- 1. gather: counts, then the rows, by ranges of reads
+            const double tg0 = brec_now();
+            int nt = c->threads < 1 ? 1 : c->threads;
+            if ((i64)nt > (n_pairs + 255) / 256) nt = (int)((n_pairs + 255) / 256);
+            std::vector<i64> cig_at((size_t)nt + 1, 0), mm_at((size_t)nt + 1, 0);
+            auto each = [&](const std::function<void(int)>& f) {
+                std::vector<std::thread> th;
+                for (int t = 1; t < nt; ++t) th.emplace_back(f, t);
+                f(0);
+                for (auto& t : th) t.join();
+            };
+            each([&](int t) { i64 ca = 0, ma = 0; brec_gather(res, n_reads * t / nt, n_reads * (t + 1) / nt, nullptr, nullptr, nullptr, nullptr, ca, ma); cig_at[(size_t)t + 1] = ca; mm_at[(size_t)t + 1] = ma; });
+            for (int t = 0; t < nt; ++t) { cig_at[(size_t)t + 1] += cig_at[(size_t)t]; mm_at[(size_t)t + 1] += mm_at[(size_t)t]; }
+            s_row = sl.add((size_t)n_reads * LH_BREC_SLOTS * sizeof(BrecRow)); s_rd = sl.add((size_t)n_reads * 4 * sizeof(double));
+            s_cig = sl.add((size_t)cig_at[(size_t)nt] * 4); s_mm = sl.add((size_t)mm_at[(size_t)nt] * 8);
+            rc = brec_pinned(&B->h_stage, &B->h_stage_cap, sl.total);
+            if (!rc) rc = brec_dev(B->stage, sl.total);
+            if (rc) return rc;
+            hs = (uint8_t*)B->h_stage;
+            each([&](int t) {
+                i64 ca = cig_at[(size_t)t], ma = mm_at[(size_t)t];
+                brec_gather(res, n_reads * t / nt, n_reads * (t + 1) / nt, (BrecRow*)(hs + s_row), (double*)(hs + s_rd), (uint32_t*)(hs + s_cig), (int32_t*)(hs + s_mm), ca, ma);
+            });
+            c->t[0] = brec_now() - tg0;
+        }
         // ---- 2. upload: the rows in one copy, the batch's text arenas and offsets as they are, the writer's small tables
         std::vector<i64> cname_off((size_t)n_contigs + 1, 0);
         std::string cname;
@@ -168,12 +237,7 @@ int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
         const size_t a_boff = sec(bucket_off.data(), bucket_off.size() * 4), a_bucket = sec(bucket.data(), bucket.size() * 4);
         rc = brec_dev(B->text, tl.total);
         if (!rc) rc = brec_dev(B->plan, (size_t)n_slots * sizeof(BrecPlan));
-        BrecLayout wl;
-        const size_t N = (size_t)n_slots;
-        const size_t w_key0 = wl.add(N * 4), w_key1 = wl.add(N * 4), w_val0 = wl.add(N * 4), w_val1 = wl.add(N * 4);
-        const size_t w_sz = wl.add((N + 1) * 8), w_offbc = wl.add((N + 1) * 8), w_ssz = wl.add((N + 1) * 8), w_sscan = wl.add((N + 1) * 8), w_offf = wl.add(N * 8);
-        const size_t w_fend = wl.add((size_t)n_out * 8), w_fbase = wl.add((size_t)n_out * 8), w_err = wl.add(16), w_wd = wl.add(LH_WD_SLOTS * 4);
-        if (!rc) rc = brec_dev(B->work, wl.total);
+        if (!rc) rc = brec_dev(B->work, wl.total);   // (after a device gather: the buffer it allocated with this size, so this keeps it and the counts and scans in it; the same for h_small below)
         size_t tmp_bytes = 16;
 #ifndef LH_EMU
         {
@@ -185,12 +249,11 @@ int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
         }
 #endif
         if (!rc) rc = brec_dev(B->tmp, tmp_bytes);
-        const size_t small_words = (size_t)n_out + 1 + 2 + LH_WD_SLOTS / 2;
-        if (!rc) rc = brec_pinned((void**)&B->h_small, &B->h_small_cap, small_words * 8);
+        if (!rc) rc = brec_pinned((void**)&B->h_small, &B->h_small_cap, (small_words + (srcs ? small_gather : 0)) * 8);
         if (rc) return rc;
         uint8_t* dt = (uint8_t*)B->text.p; uint8_t* ds = (uint8_t*)B->stage.p; uint8_t* dw = (uint8_t*)B->work.p;
         HIPCHK(hipEventRecord(B->ev[0], st));
-        HIPCHK(hipMemcpyAsync(ds, hs, sl.total, hipMemcpyHostToDevice, st));
+        if (!srcs) HIPCHK(hipMemcpyAsync(ds, hs, sl.total, hipMemcpyHostToDevice, st));
         for (const BrecUpload& u : ups) if (u.bytes) HIPCHK(hipMemcpyAsync(dt + u.at, u.src, u.bytes, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(dw + w_fend, 0xff, (size_t)n_out * 8, st));
         HIPCHK(hipMemsetAsync(dw + w_err, 0, 16 + LH_WD_SLOTS * 4, st));   // (err and the watchdog words are neighbours)
@@ -253,7 +316,17 @@ int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
         HIPCHK(hipMemcpyAsync(hsm, d_fend, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hsm + n_out, off_bc + N, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hsm + n_out + 1, d_err, 16 + LH_WD_SLOTS * 4, hipMemcpyDeviceToHost, st));
+        if (srcs) {
+            HIPCHK(hipMemcpyAsync(hsm + small_words, dw + w_gerr, 16 + LH_WD_SLOTS * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipEventSynchronize(B->ev[7]));   // the gather kernels have read the context's arrays: its next align may overwrite them
+            if (ctx_lock && ctx_lock->owns_lock()) ctx_lock->unlock();
+        }
         HIPCHK(hipStreamSynchronize(st));
+        if (srcs) {
+            const int32_t* g = (const int32_t*)(hsm + small_words);
+            for (int k = 0; k < LH_WD_SLOTS; ++k) if (g[4 + k]) return set_err(LH_E_HIP, "lh_bam_append_resident: watchdog word " + std::to_string(k) + " of k_brec_gather_fill tripped");
+            if (g[0] & LH_BREC_E_INDEX) return set_err(LH_E_HIP, "lh_bam_append_resident: the context's result changed under the gather");
+        }
         const int32_t* h_err = (const int32_t*)(hsm + n_out + 1);
         const int32_t* h_wd = h_err + 4;
         for (int k = 0; k < LH_WD_SLOTS; ++k) if (h_wd[k]) return set_err(LH_E_HIP, "lh_bam_append: watchdog word " + std::to_string(k) + " of k_brec_plan tripped");
@@ -300,6 +373,7 @@ int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
         float ms[3] = {0, 0, 0};
         HIPCHK(hipEventElapsedTime(&ms[0], B->ev[0], B->ev[1])); HIPCHK(hipEventElapsedTime(&ms[1], B->ev[2], B->ev[3])); HIPCHK(hipEventElapsedTime(&ms[2], B->ev[4], B->ev[5]));
         c->t[1] = ms[0] * 1e-3; c->t[2] = ms[1] * 1e-3; c->t[3] = ms[2] * 1e-3;
+        if (srcs) { float g = 0; HIPCHK(hipEventElapsedTime(&g, B->ev[6], B->ev[7])); c->t[0] = g * 1e-3; }   // (the read-back of the totals between the two kernels included)
     } else {   // an empty batch: the pending bytes alone (whole blocks of them are written, as the host path's flush does)
         i64 cursor = 0;
         for (int o = 0; o < n_out; ++o) { region[(size_t)o] = cursor; cursor += (i64)c->pending[(size_t)o]->size(); }
@@ -347,8 +421,61 @@ int brec_encode(lh_bgzf* z, LhBrecCall* c, lh_brec_bufs* B) {
 }
 }   // namespace
 
+// lh_bam_append_resident: the pipelines that hold the batch's result, each with its part's place in the batch (the first lane's reads first, as lh_result_download_end
+// merges them), after the checks a download makes before it trusts a result.  The caller holds the context's mutex
+static int brec_resident_srcs(lh_bgzf* z, lh_context* ctx, const lh_ingest_batch* in, std::vector<BrecSrc>* srcs) {
+    const char* const F = "lh_bam_append_resident: ";
+    if (!ctx->ran) return set_err(LH_E_ARG, std::string(F) + "nothing was aligned yet: call lh_align_resident first; nothing was appended");
+    std::vector<lh_context*> pipes(1, ctx);
+    if (lanes_split(ctx)) for (lh_context* p : ctx->more) pipes.push_back(p);
+    i64 n_reads = 0;
+    for (lh_context* p : pipes) {
+        if (!p->ran) return set_err(LH_E_ARG, std::string(F) + "nothing was aligned yet: call lh_align_resident first; nothing was appended");
+        if (p->rounds.n_rounds > 1)
+            return set_err(LH_E_ARG, std::string(F) + "the last batch was aligned in rounds: its parts' results were merged on the host already, none is resident as a whole; lh_result_download + "
+                                                      "lh_bam_append cost nothing extra there; nothing was appended");
+        if (!p->ran_inference) return set_err(LH_E_ARG, std::string(F) + "the last lh_align_resident ran without inference (lh_opts.run_inference): no read has an active alignment; nothing was appended");
+        n_reads += p->b.n_reads;
+    }
+    if (n_reads != 2 * (i64)in->batch.n_pairs)
+        return set_err(LH_E_ARG, std::string(F) + "the ingest batch has " + std::to_string(in->batch.n_pairs) + " pairs, the batch the context aligned " + std::to_string(n_reads / 2) + "; nothing was appended");
+    if (ctx->idx->device != z->device)
+        return set_err(LH_E_ARG, std::string(F) + "the context's result is on device " + std::to_string(ctx->idx->device) + ", the writer's compressor on device " + std::to_string(z->device) + "; nothing was appended");
+    i64 read0 = 0;
+    for (size_t k = 0; k < pipes.size(); ++k) {
+        lh_context* p = pipes[k];
+        BrecSrc s;
+        s.n_reads = p->b.n_reads; s.read0 = read0; s.n_cand = 0; s.R = p->R; s.S = p->S;
+        const int rc = pipe_result_check(p, &s.n_cand);
+        if (rc) { const std::string why = g_err; return set_err(rc, std::string(F) + (k ? "lane " + std::to_string(k + 1) + ": " : "") + why + "; nothing was appended"); }
+        srcs->push_back(s);
+        read0 += p->b.n_reads;
+    }
+    return LH_OK;
+}
+
 extern "C" int lh_brec_encode_(lh_bgzf* z, LhBrecCall* c) {
-    if (!z || !c || !c->res || !c->in || !c->names || !c->bucket || !c->zbuf || !c->zbuf_cap) return set_err(LH_E_ARG, "lh_bam_append: null argument");
+    if (!z || !c || (!c->res && !c->ctx) || !c->in || !c->names || !c->bucket || !c->zbuf || !c->zbuf_cap) return set_err(LH_E_ARG, "lh_bam_append: null argument");
+    if (c->ctx) {
+        // Lock order: the context's mutex, then the compressor's (the appends from a downloaded result take the compressor's alone).  The context's is held until the
+        // gather kernels have completed (brec_encode releases it on their event), so that no next lh_align_resident overwrites the arrays under them; a download in
+        // flight reads the same arrays and is no conflict
+        std::unique_lock<std::mutex> ctx_lock(c->ctx->res_mu);
+        std::vector<BrecSrc> srcs;
+        // (an ingest batch without pairs, the end of the input, has no resident counterpart: a context holds no empty batch.  It reads nothing of the context)
+        if (c->in->batch.n_pairs > 0) { const int rc = brec_resident_srcs(z, c->ctx, c->in, &srcs); if (rc) { c->refused = true; return rc; } }
+        std::lock_guard<std::mutex> lock(z->mu);
+        HIPCHK(hipSetDevice(z->device));
+        if (!z->enc) z->enc = new lh_brec_bufs();
+        const int rc = brec_encode(z, c, z->enc, &srcs, &ctx_lock);
+        if (rc) {   // nothing of this call stays in flight (the context's mutex is still held, or the gather has completed)
+            const std::string why = g_err;
+            for (lh_bgzf::Set& s : z->set) { (void)hipStreamSynchronize(s.st); s.nb = 0; }
+            (void)hipGetLastError();
+            return set_err(rc, why);
+        }
+        return LH_OK;
+    }
     const lh_result* res = c->res;
     if (res->n_reads != 2 * c->in->batch.n_pairs) return set_err(LH_E_ARG, "lh_bam_append: result and batch describe different reads");
     for (int64_t read = 0; read < res->n_reads; ++read)
@@ -356,7 +483,7 @@ extern "C" int lh_brec_encode_(lh_bgzf* z, LhBrecCall* c) {
     std::lock_guard<std::mutex> lock(z->mu);
     HIPCHK(hipSetDevice(z->device));
     if (!z->enc) z->enc = new lh_brec_bufs();
-    const int rc = brec_encode(z, c, z->enc);
+    const int rc = brec_encode(z, c, z->enc, nullptr, nullptr);
     if (rc) {   // nothing of this call stays in flight
         const std::string why = g_err;
         for (lh_bgzf::Set& s : z->set) { (void)hipStreamSynchronize(s.st); s.nb = 0; }

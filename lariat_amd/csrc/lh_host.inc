@@ -148,6 +148,7 @@ struct lh_context {
     float tms[LH_NSTAGE];
     int n_t = 0;
     bool resident = false, ran = false;
+    std::mutex res_mu;   // (the first pipeline's) held by lh_align_resident and lh_stage_dump_resident, and by lh_bam_append_resident while its gather kernels read the result arrays.  Lock order: this, then a compressor's
     // resident input batches: slot 0 holds capacity-sized buffers allocated at creation, further slots own exact-size copies
     struct DevBatch {
         BatchView v;    // the slot's batch (pipe_upload_slot)
@@ -986,6 +987,7 @@ static bool lanes_split(const lh_context* c);   // (lh_lanes.inc)
 
 int lh_stage_dump_resident(lh_context* c, const lh_opts* opts, lh_stage_dump** out) {
     if (!c || !opts || !out) return set_err(LH_E_ARG, "lh_stage_dump_resident: null argument");
+    std::lock_guard<std::mutex> res_lock(c->res_mu);   // (the dump reruns the front half over the result arrays: as lh_align_resident, not under lh_bam_append_resident's gather)
     {   // the dump shows mem_align1_core's output, i.e. BEFORE mate rescue: rerun the front half only
         if (lanes_split(c))
             return set_err(LH_E_ARG, "lh_stage_dump_resident: the resident batch is split over several lanes (create the context with lanes = 1 for stage dumps)");

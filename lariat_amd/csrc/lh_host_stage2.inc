@@ -429,26 +429,12 @@ __global__ void __launch_bounds__(256) k_status_or(int n, const int32_t* __restr
     for (int m = 32; m >= 1; m >>= 1) v |= __shfl_xor(v, m);
     if (LANE() == 0 && v) atomicOr(out, v);
 }
-// The result leaves in two steps so that a host with ONE context can have batch k's download under batch k + 1's kernels (the reference
-// double-buffers its work units the same way: lariat.go:333, bamwriter.go:188): pipe_download_begin checks the batch's status, packs the
-// variable-length arrays and ENQUEUES the device-to-host copies on the context's copy stream; pipe_download_end waits for them and hands
-// out the result.  In between the host may call lh_align_resident for the next batch: its kernels up to the mate rescue do not touch the
-// result arrays, and it waits for the copies (ev_dl) before the first one that does.
-static int pipe_download_begin(lh_context* c) {
-    if (!c) return set_err(LH_E_ARG, "lh_result_download: null argument");
-    if (!c->ran) return set_err(LH_E_ARG, "nothing to download: call lh_align_resident first");
-    if (c->dl_pending) return set_err(LH_E_ARG, "lh_result_download_begin: the previous download has not been collected (lh_result_download_end)");
-    if (c->rounds.n_rounds > 1) {   // a batch aligned in rounds: every part was downloaded and merged inside lh_align_resident, nothing is left to enqueue
-        if (!c->round_result) return set_err(LH_E_ARG, "lh_result_download: the result of a batch aligned in rounds is handed out once");
-        lh_result* r = c->round_result;
-        c->round_result = nullptr;
-        c->dl_pending = true;
-        c->dl_finish = [r](lh_result** out) -> int { *out = r; return LH_OK; };
-        return LH_OK;
-    }
+// What a pipeline's result must pass before anything reads it, the download (pipe_download_begin) and the BAM encoder's device gather (lh_bam_append_resident) alike:
+// no read over a per-read limit (named in the message), no overflowed workspace, a candidate total within the pools, no watchdog word.  *n_cand: the candidate total
+static int pipe_result_check(lh_context* c, i64* n_cand) {
     HIPCHK(hipSetDevice(c->idx->device));
     const int N = c->b.n_reads;
-    // three small read-backs first: the OR of the status words, the candidate total, the packed CIGAR / mismatch totals
+    // two small read-backs first: the OR of the status words, the candidate total
     int32_t* const status_or = &c->d_aln_count->flat;   // (K7's counter: free by now)
     HIPCHK(hipMemsetAsync(status_or, 0, sizeof(int32_t), c->stream));
     if (N > 0) LH_LAUNCH(k_status_or, (N + 255) / 256, 256, c->stream, N, (const int32_t*)c->d_status, status_or);
@@ -483,6 +469,29 @@ static int pipe_download_begin(lh_context* c) {
                 return set_err(LH_E_HIP, "a kernel watchdog tripped (slot " + std::to_string(i) + "): the batch's results are not trustworthy");
             }
     }
+    *n_cand = C;
+    return LH_OK;
+}
+// The result leaves in two steps so that a host with ONE context can have batch k's download under batch k + 1's kernels (the reference
+// double-buffers its work units the same way: lariat.go:333, bamwriter.go:188): pipe_download_begin checks the batch's status, packs the
+// variable-length arrays and ENQUEUES the device-to-host copies on the context's copy stream; pipe_download_end waits for them and hands
+// out the result.  In between the host may call lh_align_resident for the next batch: its kernels up to the mate rescue do not touch the
+// result arrays, and it waits for the copies (ev_dl) before the first one that does.
+static int pipe_download_begin(lh_context* c) {
+    if (!c) return set_err(LH_E_ARG, "lh_result_download: null argument");
+    if (!c->ran) return set_err(LH_E_ARG, "nothing to download: call lh_align_resident first");
+    if (c->dl_pending) return set_err(LH_E_ARG, "lh_result_download_begin: the previous download has not been collected (lh_result_download_end)");
+    if (c->rounds.n_rounds > 1) {   // a batch aligned in rounds: every part was downloaded and merged inside lh_align_resident, nothing is left to enqueue
+        if (!c->round_result) return set_err(LH_E_ARG, "lh_result_download: the result of a batch aligned in rounds is handed out once");
+        lh_result* r = c->round_result;
+        c->round_result = nullptr;
+        c->dl_pending = true;
+        c->dl_finish = [r](lh_result** out) -> int { *out = r; return LH_OK; };
+        return LH_OK;
+    }
+    const int N = c->b.n_reads;
+    i64 C = 0;
+    { int rc = pipe_result_check(c, &C); if (rc) return rc; }
     { int rc = run_scan(c, (int)C, c->R.n_cigar, 0, 0, c->d_cigar_off); if (rc) return rc; }
     { int rc = run_scan(c, (int)C, c->R.n_mm, 0, 0, c->d_mm_off); if (rc) return rc; }
     i64 tc = 0, tm = 0;

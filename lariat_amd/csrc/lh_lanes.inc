@@ -121,6 +121,7 @@ int lh_batch_select(lh_context* c, int32_t slot) {
 
 int lh_align_resident(lh_context* c, const lh_opts* opts) {
     if (!c || !opts) return set_err(LH_E_ARG, "lh_align_resident: null argument");
+    std::lock_guard<std::mutex> res_lock(c->res_mu);   // (lh_bam_append_resident's gather may still be reading the previous result)
     if (!lanes_split(c)) {
         for (lh_context* p : c->more) p->rounds.clear();   // (lh_last_rounds: they took no part)
         return pipe_align(c, opts);
