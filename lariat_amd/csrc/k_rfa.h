@@ -597,13 +597,14 @@ __global__ void __launch_bounds__(64) k_rfa_tag_w(DOpts o, const u64* __restrict
         X(mflag, int32_t, NC) X(P, double, NC)                                                                                                                            \
         X(dk0, u64, nR) X(dk1, u64, nR) X(dk2, u64, nR) X(dk3, u64, nR) X(htab, int32_t, (size_t)1 << hbits)                                                              \
         X(gstk, int32_t, 3 * LH_GOSORT_STK * 64)
+// one table of the list: its size alone (LH_RFA_SZ), or its place in `slab` as T.ptr (LH_RFA_CARVE); `so` is the running offset, every table 8-byte aligned
+#define LH_RFA_SZ(ptr, type, count) { so = (so + 7) & ~(size_t)7; so += sizeof(type) * (size_t)(count); }
+#define LH_RFA_CARVE(ptr, type, count) { so = (so + 7) & ~(size_t)7; T.ptr = (type*)(slab + so); so += sizeof(type) * (size_t)(count); }
 __device__ __forceinline__ size_t rfa_carve_bytes(int NC, int nR, int ncmax) {
     int hbits = 6;
     while ((1 << hbits) < 2 * nR) ++hbits;
     size_t so = 0;
-#define LH_RFA_SZ(ptr, type, count) { so = (so + 7) & ~(size_t)7; so += sizeof(type) * (size_t)(count); }
     LH_RFA_CARVE_LIST(LH_RFA_SZ)
-#undef LH_RFA_SZ
     return (so + 7) & ~(size_t)7;
 }
 
@@ -696,6 +697,758 @@ __device__ int lh_rfa_bcstat[4096][8];   // per barcode (index mod 4096): 10 ns 
 #endif
 #define LH_RFA_WAVES 4   // waves per SIMD the register budget is sized for (128 VGPRs + 64 spilled: the kernel waits on memory, 4 waves hide more of it than 2 waves of 190 registers)
 #endif
+#ifdef LH_RFA_PROF
+#define RFA_PROF_PARAM , unsigned long long& prof_t_   // a phase with profile marks inside takes the running clock
+#define RFA_PROF_ARG , prof_t_
+#else
+#define RFA_PROF_PARAM
+#define RFA_PROF_ARG
+#endif
+
+// ---- The barcode program in phases.  Nine of them are functions, called from k_rfa's barcode loop (markBest's step 2, the optimizer, the probability sums and the molecule status
+// stay in the loop's body: lifted, each moved the small instance's code); each phase below restates one function of lariat.go and says what it reads, what it writes and
+// what it leaves valid for the phases after it, of three places: T (RfaTab, the slab), H (RfaHot: T's hot tables for k_rfa<0>, LDS behind the staging for k_rfa<1>) and
+// lds_raw.  lds_raw is one buffer re-used phase by phase — contig tables (grouping) | keys and places (position sort) | a tile's records and read numbers (markBest,
+// step 1) | fastScore's source staging (optimizer, probability sums) | the lanes' top-15 scores (estimateMapQualities) —: "lds_raw: scratch" below means the phase
+// leaves nothing there a later phase reads.  The small instance's H, [RFA_HOT_OFF, RFA_HOT_OFF + RFA_HOT_BYTES) of lds_raw, is written from scrapMolecules on — markBest's
+// tiles are done by then —, last read by the molecule penalty — the top-15 scores come after it; nothing else touches that range in between.
+// R (the candidates) is read-only throughout; of S every phase names the columns it writes.
+
+// a barcode's scalars as a phase sees them.  The barcode loop keeps them as its own locals and hands each phase a fresh copy, with what the earlier phases returned filled in:
+// one struct that lives across the whole loop body cost k_rfa<1> 20 B of scratch, a lambda building the copy from named fields 24 B, a positional copy per call none
+struct RfaBc {
+    int bc, r0, nR, NC;   // the barcode; its first read, its reads, its candidates
+    i64 c_lo;             // its first candidate
+    int ncmax;            // (the carve) the index's contigs + 2
+    size_t best_cap;      // (the carve) words the slab has left for T.bestT
+    int do_rfa;
+    int ncont, NCf;       // (rfa_group_contigs) contigs present, filtered candidates
+    int Mraw, M;          // molecules before (rfa_infer_molecules) and after scrapMolecules (rfa_scrap_molecules)
+};
+// slot offsets of the contig lists from their sizes scnt[0 .. ncont) (both grouping variants): T.coff[0 .. ncont], and scnt becomes each list's running write position.
+// Returns NCf, the filtered candidates.
+__device__ __forceinline__ int rfa_slot_offsets(const RfaTab& T, int32_t* scnt, int ncont, int lane) {
+    int NCf = 0;
+    for (int base = 0; base < ncont; base += 64) {
+        const int k = base + lane;
+        const int c = k < ncont ? scnt[k] : 0;
+        const int inc = wave_scan_add_i32(c);
+        EMU_SYNC();
+        if (k < ncont) { T.coff[k] = NCf + inc - c; scnt[k] = NCf + inc - c; }
+        NCf += wave_readlane(inc, 63);
+    }
+    if (lane == 0) T.coff[ncont] = NCf;
+    WAVE_SYNC();
+    return NCf;
+}
+
+// positions: the filtered candidates grouped by contig in first-seen order, candidate order inside a contig (the lists sort.Sort(ByPosition) is run on, lariat.go:1545-1547).
+// Reads: R.in_filtered, R.rid.  Writes and leaves: T.kidx [NC], T.coff [ncont + 1], T.plist [NCf]; the contig tables it needs meanwhile are in lds_raw (scratch) or, for
+// an index of more contigs than LH_RFA_NCONT_LDS, in T.seen_rid / T.ccnt (scratch).  Returns NCf; *ncont_out: the contigs present.
+template <int SMALL>
+__device__ __forceinline__ int rfa_group_contigs(const DCand& R, const RfaTab& T, const RfaBc& B, int lane, uint8_t* lds_raw, int* ncont_out) {
+    const i64 c_lo = B.c_lo;
+    const int NC = B.NC, ncmax = B.ncmax;
+    int ncont = 0, NCf = 0;
+    if (!SMALL && ncmax <= LH_RFA_NCONT_LDS && NC > 256) {
+        // (r06) a large barcode, a contig table that fits LDS: the contigs' first-seen order from one atomic minimum per candidate (the smallest candidate index
+        // that names the contig), slot sizes from one atomic add, and the stable placement from the lanes that share a slot — found with one ballot per bit of
+        // the slot number, not one loop turn per slot present in the chunk (a read on repeat families names thirty contigs: the three passes were a sixth of the
+        // kernel for a barcode of 10,000 candidates, most of it loop turns and a 36-deep search per candidate).
+        int32_t* const fs = (int32_t*)lds_raw;                          // [ncmax] by contig + 1: its first candidate, then its slot
+        int32_t* const scnt2 = (int32_t*)lds_raw + LH_RFA_NCONT_LDS;    // [ncont] slot sizes, then running write positions
+        for (int x = lane; x < ncmax; x += 64) fs[x] = 0x7fffffff;
+        WAVE_SYNC();
+        for (int a = lane; a < NC; a += 64) if (R.in_filtered[c_lo + a]) atomicMin(&fs[R.rid[c_lo + a] + 1], a);   // (+ 1: a read without a region has a placeholder on contig -1, a group of its own)
+        WAVE_SYNC();
+        // the contigs present, in the order of their first candidates: rank by counting (a few dozen of them)
+        for (int base = 0; base < ncmax; base += 64) {
+            const int x = base + lane;
+            const int f = x < ncmax ? fs[x] : 0x7fffffff;
+            int rank = -1;
+            if (f != 0x7fffffff) { rank = 0; for (int y = 0; y < ncmax; ++y) rank += fs[y] < f; }
+            const u64 pm = __ballot(rank >= 0);
+            if (rank >= 0) { T.seen_rid[rank] = x; T.ccnt[x] = rank; }
+            ncont += __popcll(pm);
+        }
+        WAVE_SYNC();
+        for (int x = lane; x < ncmax; x += 64) fs[x] = fs[x] != 0x7fffffff ? T.ccnt[x] : -1;   // contig -> slot
+        for (int k = lane; k < ncont; k += 64) scnt2[k] = 0;
+        WAVE_SYNC();
+        for (int a = lane; a < NC; a += 64) {
+            const int k = R.in_filtered[c_lo + a] ? fs[R.rid[c_lo + a] + 1] : -1;
+            T.kidx[a] = k;
+            if (k >= 0) atomicAdd(&scnt2[k], 1);
+        }
+        WAVE_SYNC();
+        NCf = rfa_slot_offsets(T, scnt2, ncont, lane);   // scnt2 becomes the running write position
+        int kbits = 1;
+        while ((1 << kbits) < ncont) ++kbits;
+        for (int base = 0; base < NC; base += 64) {   // stable placement: candidate order inside a slot
+            const int a = base + lane;
+            const int k = a < NC ? T.kidx[a] : -1;
+            const int valid = k >= 0;
+            u64 peers = __ballot(valid);
+            for (int b = 0; b < kbits; ++b) { const u64 bb = __ballot(valid && ((k >> b) & 1)); peers &= ((k >> b) & 1) ? bb : ~bb; }
+            const int at = valid ? scnt2[k] : 0;
+            EMU_SYNC();
+            if (valid) {
+                T.plist[at + lanes_below(peers, lane)] = a;
+                if (lanes_below(peers, lane) == 0) scnt2[k] = at + __popcll(peers);
+            }
+            WAVE_SYNC();
+        }
+    } else {
+    // pass A: contig slot of every candidate (first-seen numbering) and the slot sizes
+    int32_t* const seen = SMALL || ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw : T.seen_rid;
+    int32_t* const scnt = SMALL || ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw + LH_RFA_NCONT_LDS : T.ccnt;
+    for (int base = 0; base < NC; base += 64) {
+        int a = base + lane;
+        int valid = a < NC && R.in_filtered[c_lo + a];
+        int rid = valid ? R.rid[c_lo + a] : 0;
+        int k = -1;
+        if (valid) for (int j = ncont - 1; j >= 0; --j) if (seen[j] == rid) { k = j; break; }
+        u64 un = __ballot(valid && k < 0);
+        while (un) {   // contigs met for the first time, in candidate order
+            int leader = __ffsll((unsigned long long)un) - 1;
+            int lrid = wave_readlane(rid, leader);
+            if (lane == 0) { seen[ncont] = lrid; scnt[ncont] = 0; }
+            if (valid && k < 0 && rid == lrid) k = ncont;
+            ncont++;
+            un = __ballot(valid && k < 0);
+        }
+        WAVE_SYNC();
+        if (a < NC) T.kidx[a] = valid ? k : -1;
+        u64 rem = __ballot(valid);
+        while (rem) {
+            int kk = wave_readlane(k, __ffsll((unsigned long long)rem) - 1);
+            u64 m = __ballot(valid && k == kk);
+            if (lane == 0) scnt[kk] += __popcll(m);
+            rem &= ~m;
+        }
+        WAVE_SYNC();
+    }
+    NCf = rfa_slot_offsets(T, scnt, ncont, lane);   // scnt becomes the running write position
+    // pass B: stable placement
+    for (int base = 0; base < NC; base += 64) {
+        int a = base + lane;
+        int k = a < NC ? T.kidx[a] : -1;
+        int valid = k >= 0;
+        u64 rem = __ballot(valid);
+        while (rem) {
+            int kk = wave_readlane(k, __ffsll((unsigned long long)rem) - 1);
+            u64 m = __ballot(valid && k == kk);
+            int at = scnt[kk];
+            EMU_SYNC();
+            if (valid && k == kk) T.plist[at + lanes_below(m, lane)] = a;
+            if (lane == 0) scnt[kk] = at + __popcll(m);
+            EMU_SYNC();
+            rem &= ~m;
+        }
+    }
+    WAVE_SYNC();
+    }
+    *ncont_out = ncont;
+    return NCf;
+}
+
+// sort.Sort(ByPosition) per contig list (lariat.go:1545-1547), Go's order of equal positions included.
+// Reads: T.plist, T.coff, R.pos.  Writes and leaves: T.plist, every contig list in position order.  Scratch: lds_raw (keys and places, the network's block), shi[6 .. 7],
+// T.gstk, and for lists beyond the LDS buffer T.sval (keys) and T.molraw / T.rdl / T.firstf / T.molc / T.ppos (queues of ranges, ranks): all free until inferMolecules.
+template <int SMALL>
+__device__ __forceinline__ void rfa_sort_positions(const DCand& R, const RfaTab& T, const RfaBc& B, int lane, uint8_t* lds_raw, int32_t* shi RFA_PROF_PARAM) {
+    const i64 c_lo = B.c_lo;
+    const int NCf = B.NCf, ncont = B.ncont;
+    i64* const spos = (i64*)lds_raw;
+    int32_t* const sidx = (int32_t*)(lds_raw + 8 * LH_RFA_SORT_LDS);
+    // sort.Sort(ByPosition) per contig (lariat.go:1545-1547), one lane per contig; keys staged in LDS when they fit
+    if (NCf <= LH_RFA_SORT_LDS && ncont <= 8) {
+        // Few contigs: the wave sorts one contig at a time by ranking (every lane counts the smaller keys of its elements).
+        // Go's sort is unstable, but with all keys different there is only one sorted order; a contig with two equal
+        // positions is sorted again by the serial restatement of Go's algorithm.
+        for (int i = lane; i < NCf; i += 64) { sidx[i] = T.plist[i]; spos[i] = R.pos[c_lo + T.plist[i]]; }
+        WAVE_SYNC();
+        for (int k = 0; k < ncont; ++k) {
+            int b0 = T.coff[k], n = T.coff[k + 1] - b0;
+            i64* kp = spos + b0;
+            int32_t* ip = sidx + b0;
+            int tie = 0;
+            for (int e = lane; e < n; e += 64) {
+                i64 key = kp[e];
+                int rank = 0;
+                for (int j = 0; j < n; ++j) { i64 kj = kp[j]; rank += kj < key; tie |= (kj == key) & (j != e); }
+                T.plist[b0 + rank] = ip[e];
+            }
+            if (__any(tie)) {
+                WAVE_SYNC();
+                if (lane == 0)
+                    dev_gosort(n, [&](int i, int j) { return kp[i] < kp[j]; },
+                               [&](int i, int j) { i64 t = kp[i]; kp[i] = kp[j]; kp[j] = t; int u = ip[i]; ip[i] = ip[j]; ip[j] = u; }, T.gstk + lane, 64);
+                WAVE_SYNC();
+                for (int e = lane; e < n; e += 64) T.plist[b0 + e] = ip[e];
+            }
+        }
+    } else if (SMALL || NCf <= LH_RFA_SORT_LDS) {
+        for (int i = lane; i < NCf; i += 64) { sidx[i] = T.plist[i]; spos[i] = R.pos[c_lo + T.plist[i]]; }
+        WAVE_SYNC();
+        for (int k = lane; k < ncont; k += 64) {
+            int b0 = T.coff[k], n = T.coff[k + 1] - b0;
+            i64* kp = spos + b0;
+            int32_t* ip = sidx + b0;
+            dev_gosort(n, [&](int i, int j) { return kp[i] < kp[j]; },
+                       [&](int i, int j) { i64 t = kp[i]; kp[i] = kp[j]; kp[j] = t; int u = ip[i]; ip[i] = ip[j]; ip[j] = u; }, T.gstk + lane, 64);
+        }
+        WAVE_SYNC();
+        for (int i = lane; i < NCf; i += 64) T.plist[i] = sidx[i];
+    } else {
+        // More candidates than the LDS buffer holds (a barcode on repeat families has thousands; the reader's cap is 30,000 pairs).  Contig by contig (r05):
+        // a contig's list that fits the buffer is staged there and sorted by ranking, as above — with all keys different there is only one sorted order; two
+        // equal positions: Go's algorithm, serially, in LDS —; a longer one is sorted in memory with the ranges of Go's quickSort spread over the lanes
+        // (lh_sort.h: wave_gosort; keys next to the list in sval, free until the molecules are scored; molraw / rdl / firstf hold the queue of ranges).
+        // (All of them at once in memory, the r04 form, was 10 % of the kernel on the repeat input: the first levels of every quickSort are one lane's.)
+        i64* const kpg = (i64*)T.sval;
+        int32_t* const pl = T.plist;
+        for (int k = 0; k < ncont; ++k) {
+            const int b0 = T.coff[k], n = T.coff[k + 1] - b0;
+#ifdef LH_RA_HIST
+            if (lane == 0) { atomicAdd(&lh_rfa_hist2[0], 1ull); atomicMax(&lh_rfa_hist2[1], (unsigned long long)n); if (n > LH_RFA_SORT_LDS) atomicAdd(&lh_rfa_hist2[2], 1ull); if (n > LH_RFA_LDS_BYTES / 4) atomicAdd(&lh_rfa_hist2[3], 1ull); atomicAdd(&lh_rfa_hist2[4], (unsigned long long)n * n); }
+#endif
+            if (n < 2) continue;
+            if (n > 64 && n < (1 << 20)) {
+                // (r06) a list of more than a wave's worth is put in order by a sorting NETWORK on packed words ((position - smallest) << 20 | place in the list), in the
+                // slab (sval, free until the molecules are scored) — instead of by ranking (every lane counting the smaller keys
+                // of its elements: n^2 / 64 steps; 2,000 entries of one contig, common for a 1,000-pair barcode with a twentieth of its pairs on repeat families, were
+                // 62,000 steps a list and the position sorts a third of the kernel).  With all keys different there is only one sorted order, whatever the algorithm;
+                // two equal positions (adjacent after the sort): Go's algorithm on the list as it was, below.
+                u64* const bk = (u64*)kpg + b0;   // (always in the slab: a pointer that is LDS for short lists and memory for long ones is a flat one — that form faulted on the device, and this one measured faster)
+                WAVE_SYNC();   // the previous contig's keys have been read
+                RFA_PROF(1)
+                // the positions, gathered ONCE (eight independent reads a lane in flight) into the slab next to the list, and the smallest of them
+                i64 mn = 0x7fffffffffffffffll;
+                for (int i0 = lane; i0 < n; i0 += 64 * 8) {
+                    int ca[8];
+                    i64 x[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) ca[u] = i0 + 64 * u < n ? pl[b0 + i0 + 64 * u] : -1;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) x[u] = ca[u] >= 0 ? R.pos[c_lo + ca[u]] : 0x7fffffffffffffffll;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { if (ca[u] >= 0) bk[i0 + 64 * u] = (u64)x[u]; mn = mn < x[u] ? mn : x[u]; }
+                }
+                mn = wave_min_i64(mn);
+                RFA_PROF(22)
+                if (n <= LH_RFA_NET_BLOCK) {
+                    // up to 1,024 keys: the network runs in LDS (a pass is a round trip to LDS, not to the slab: thirty lists a barcode, 36 - 55 passes each) and its result is
+                    // copied to the slab, where everything that follows reads it — through its own pointer, never one that is LDS for some lists and memory for others
+                    u64* const lk = (u64*)lds_raw;
+                    for (int i = lane; i < n; i += 64) lk[i] = (u64)((i64)bk[i] - mn) << 20 | (u64)i;
+                    WAVE_SYNC();
+                    RFA_PROF(23)
+                    wave_bitonic_u64(lk, n, lane);
+                    for (int i = lane; i < n; i += 64) bk[i] = lk[i];
+                    WAVE_SYNC();
+                } else {
+                    // longer: the network block by block through LDS, a few passes over the list in the slab between them (lh_sort.h)
+                    for (int i = lane; i < n; i += 64) bk[i] = (u64)((i64)bk[i] - mn) << 20 | (u64)i;
+                    WAVE_SYNC();
+                    RFA_PROF(23)
+                    wave_bitonic_u64_blocks<LH_RFA_NET_BLOCK>(bk, n, (u64*)lds_raw, lane);
+                }
+                RFA_PROF(19)
+                int tie = 0;
+                for (int e = lane; e < n; e += 64) {
+                    const u64 w = bk[e];
+                    if (e + 1 < n) tie |= (bk[e + 1] >> 20) == (w >> 20);
+                    T.molraw[b0 + e] = pl[b0 + (int)(w & 0xfffffu)];
+                }
+                const int tied = __any(tie);
+#ifdef LH_RA_HIST
+                if (tied && lane == 0) atomicAdd(&lh_rfa_hist2[5], 1ull);
+#endif
+                WAVE_SYNC();
+                if (!tied) {
+                    for (int e = lane; e < n; e += 64) pl[b0 + e] = T.molraw[b0 + e];
+                    WAVE_SYNC();
+                    RFA_PROF(20)
+                    continue;
+                }
+                RFA_PROF(20)
+                if (n <= LH_RFA_TIE_LDS) {
+                    // Two equal positions: Go's algorithm (its ranges spread over the lanes) on the list AS IT WAS — but on one word per entry in LDS: Less only asks which of two
+                    // positions is smaller, so a position's dense RANK (from the network's order: equal positions share one) answers for it, and (rank << 12 | place) is a
+                    // 32-bit word that a Swap moves whole.  Up to 2,304 entries instead of 768 (12 bytes each: position and place), and lists of 800 - 2,300 entries — two reads
+                    // at the same offset of a 300-bp family tie on EVERY copy — were sorted in memory, two dependent reads per comparison.
+                    int carry = 0;
+                    for (int e0 = 0; e0 < n; e0 += 64) {
+                        const int e = e0 + lane;
+                        int fl = 0;
+                        u64 w = 0;
+                        if (e < n) { w = bk[e]; fl = e > 0 && (bk[e - 1] >> 20) != (w >> 20); }
+                        const int rk = carry + wave_scan_add_i32(fl);
+                        if (e < n) T.rdl[b0 + (int)(w & 0xfffffu)] = rk;   // (rdl: free until inferMolecules)
+                        carry = wave_readlane(rk, 63);
+                    }
+                    WAVE_SYNC();
+                    uint32_t* const g32 = (uint32_t*)lds_raw;
+                    for (int i = lane; i < n; i += 64) g32[i] = (uint32_t)T.rdl[b0 + i] << 12 | (uint32_t)i;
+                    if (lane == 0) { shi[6] = 0; shi[7] = n; }
+                    WAVE_SYNC();
+                    wave_gosort(1, shi + 6, [&](int i, int j) { return (g32[i] >> 12) < (g32[j] >> 12); },
+                                [&](int i, int j) { const uint32_t t = g32[i]; g32[i] = g32[j]; g32[j] = t; }, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);   // (molc, ppos: set after the sorts)
+                    WAVE_SYNC();
+                    for (int e = lane; e < n; e += 64) T.molc[b0 + e] = pl[b0 + (int)(g32[e] & 0xfffu)];   // (molc: set after the sorts)
+                    WAVE_SYNC();
+                    for (int e = lane; e < n; e += 64) pl[b0 + e] = T.molc[b0 + e];
+                    WAVE_SYNC();
+                    RFA_PROF(21)
+                    continue;
+                }
+                {
+                    // (r06, late) longer still — several thousand entries on one contig, a 400-pair barcode on repeat families — and two equal positions: Go's algorithm
+                    // on (rank << 20 | place) words in the slab, where the network's keys were: its long ranges are partitioned by the whole wave there (coalesced passes),
+                    // and every range of up to a block's length is sorted in LDS with the depth the long sort has left it.  (It was Go's algorithm on positions and
+                    // places in memory, a lane a range: a sixth of the kernel on such barcodes.)
+                    int carry = 0;
+                    for (int e0 = 0; e0 < n; e0 += 64) {
+                        const int e = e0 + lane;
+                        int fl = 0;
+                        u64 w = 0;
+                        if (e < n) { w = bk[e]; fl = e > 0 && (bk[e - 1] >> 20) != (w >> 20); }
+                        const int rk = carry + wave_scan_add_i32(fl);
+                        if (e < n) T.rdl[b0 + (int)(w & 0xfffffu)] = rk;
+                        carry = wave_readlane(rk, 63);
+                    }
+                    WAVE_SYNC();
+                    for (int i = lane; i < n; i += 64) bk[i] = (u64)(uint32_t)T.rdl[b0 + i] << 20 | (u64)i;
+                    WAVE_SYNC();
+                    auto less_g = [&](int i, int j) { return (bk[i] >> 20) < (bk[j] >> 20); };
+                    auto swp_g = [&](int i, int j) { const u64 t = bk[i]; bk[i] = bk[j]; bk[j] = t; };
+                    const int nq = wave_gosort_split(0, n, LH_RFA_NET_BLOCK, less_g, swp_g, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);
+                    const int qo = n / 16 + 64;   // (the ranges of the sorts in LDS wait behind those of the long one: fewer than n / 25 of the latter, at most a block's length of the former)
+                    u64* const lk = (u64*)lds_raw;
+                    for (int q = 0; q < nq; ++q) {
+                        const int a = T.molraw[q], len = T.rdl[q] - a, d = T.firstf[q];
+                        if (len < 2) continue;
+                        if (len > LH_RFA_NET_BLOCK) {   // (its depth used up before it was short: Go's heap sort, where it lies)
+                            WAVE_SYNC();
+                            if (lane == 0) { shi[6] = a; shi[7] = a + len; }
+                            WAVE_SYNC();
+                            wave_gosort(1, shi + 6, less_g, swp_g, T.molraw + qo, T.rdl + qo, T.firstf + qo, T.molc, T.ppos, d);
+                            WAVE_SYNC();
+                            continue;
+                        }
+                        WAVE_SYNC();
+                        for (int i = lane; i < len; i += 64) lk[i] = bk[a + i];
+                        if (lane == 0) { shi[6] = 0; shi[7] = len; }
+                        WAVE_SYNC();
+                        wave_gosort(1, shi + 6, [&](int i, int j) { return (lk[i] >> 20) < (lk[j] >> 20); }, [&](int i, int j) { const u64 t = lk[i]; lk[i] = lk[j]; lk[j] = t; },
+                                    T.molraw + qo, T.rdl + qo, T.firstf + qo, T.molc, T.ppos, d);
+                        WAVE_SYNC();
+                        for (int i = lane; i < len; i += 64) bk[a + i] = lk[i];
+                    }
+                    WAVE_SYNC();
+                    for (int e = lane; e < n; e += 64) T.molc[b0 + e] = pl[b0 + (int)(bk[e] & 0xfffffu)];
+                    WAVE_SYNC();
+                    for (int e = lane; e < n; e += 64) pl[b0 + e] = T.molc[b0 + e];
+                    WAVE_SYNC();
+                    RFA_PROF(21)
+                    continue;
+                }
+            }
+            if (n > LH_RFA_SORT_LDS) {
+                for (int i = lane; i < n; i += 64) kpg[b0 + i] = R.pos[c_lo + pl[b0 + i]];
+                WAVE_SYNC();
+                wave_gosort(1, T.coff + k, [&](int i, int j) { return kpg[i] < kpg[j]; },
+                            [&](int i, int j) { i64 t = kpg[i]; kpg[i] = kpg[j]; kpg[j] = t; int u = pl[i]; pl[i] = pl[j]; pl[j] = u; }, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);
+                WAVE_SYNC();
+                continue;
+            }
+            WAVE_SYNC();   // the previous contig's keys have been read
+            for (int i = lane; i < n; i += 64) { const int a = pl[b0 + i]; sidx[i] = a; spos[i] = R.pos[c_lo + a]; }
+            WAVE_SYNC();
+            int tie = 0;
+            for (int e = lane; e < n; e += 64) {
+                const i64 key = spos[e];
+                int rank = 0;
+                for (int j = 0; j < n; ++j) { const i64 kj = spos[j]; rank += kj < key; tie |= (kj == key) & (j != e); }
+                pl[b0 + rank] = sidx[e];
+            }
+            if (__any(tie)) {
+                // (r05: two reads drawn on one 300-bp family at the same offset have equal positions on EVERY copy — most of a repeat barcode's larger contigs have a tie.
+                // Go's algorithm then, with the ranges of its quickSort spread over the lanes, on the keys in LDS; it was one lane's)
+#ifdef LH_RA_HIST
+                if (lane == 0) atomicAdd(&lh_rfa_hist2[5], 1ull);
+#endif
+                WAVE_SYNC();
+                if (lane == 0) { shi[6] = 0; shi[7] = n; }
+                WAVE_SYNC();
+                wave_gosort(1, shi + 6, [&](int i, int j) { return spos[i] < spos[j]; },
+                            [&](int i, int j) { i64 t = spos[i]; spos[i] = spos[j]; spos[j] = t; int u = sidx[i]; sidx[i] = sidx[j]; sidx[j] = u; }, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);
+                WAVE_SYNC();
+                for (int e = lane; e < n; e += 64) pl[b0 + e] = sidx[e];
+            }
+        }
+    }
+    WAVE_SYNC();
+}
+
+// inferMolecules (lariat.go:1370-1408) over the sorted lists.
+// Reads: T.plist, T.coff, T.kidx, R.pos, S.cand_read.  Writes and leaves: T.molc, T.ppos [NC] (candidate -> raw molecule, plist index; -1: not filtered), T.molraw, T.rdl [NCf],
+// T.mstart [Mraw + 1]; T.firstf [NCf] = -1 (markBest's first step fills it).  lds_raw: untouched.  Returns Mraw.
+__device__ __forceinline__ int rfa_infer_molecules(const DCand& R, const DInf& S, const RfaTab& T, const RfaBc& B, int lane) {
+    const i64 c_lo = B.c_lo;
+    const int NC = B.NC, NCf = B.NCf, r0 = B.r0;
+    for (int a = lane; a < NC; a += 64) { T.molc[a] = -1; T.ppos[a] = -1; }
+    WAVE_SYNC();
+    // ---- inferMolecules: a gap > 50 kb (or a new contig list) starts a molecule ----
+    int Mraw = 0;
+    for (int base = 0; base < NCf; base += 64) {
+        int i = base + lane, st = 0, a = -1;
+        if (i < NCf) {
+            a = T.plist[i];
+            st = i == T.coff[T.kidx[a]];
+            if (!st) st = R.pos[c_lo + a] - R.pos[c_lo + T.plist[i - 1]] > 50000;
+        }
+        u64 mk = __ballot(st);
+        int mi = Mraw + __popcll(mk & ((2ull << lane) - 1)) - 1;
+        if (i < NCf) {
+            T.molraw[i] = mi; T.molc[a] = mi; T.ppos[a] = i; T.rdl[i] = S.cand_read[c_lo + a] - r0;
+            T.firstf[i] = -1;   // (not looked at yet: the large molecules' entries are, below, before the others)
+            if (st) T.mstart[mi] = i;
+        }
+        Mraw += __popcll(mk);
+    }
+    if (lane == 0) T.mstart[Mraw] = NCf;
+    WAVE_SYNC();
+    return Mraw;
+}
+
+// markBestAlignmentForReadInMolecule (lariat.go:1410-1463), step 1.
+// Reads: T.plist, T.rdl, T.molraw, T.mstart, S.active.  Writes and leaves: T.sval [NCf] (the entry's best pair score inside its molecule), T.firstf [NCf] (it is its read's first
+// entry there), T.psum / T.actc [NCf + 1] (exclusive counts of first / of active entries).  lds_raw: scratch, all of it (a tile's records and read numbers) — the small
+// instance's hot tables are written only after this phase.
+__device__ __forceinline__ void rfa_mark_best_step1(const DCand& R, const DInf& S, const RfaTab& T, const RfaBc& B, int lane, double improper, uint8_t* lds_raw RFA_PROF_PARAM) {
+    const i64 c_lo = B.c_lo;
+    const int NCf = B.NCf;
+    // ---- markBestAlignmentForReadInMolecule, step 1: best pair score of every entry inside its molecule; the
+    // entry's read is counted once per molecule (its first occurrence); molecules with an active alignment ----
+    // (r05) LARGE raw molecules first, from LDS.  On repeat families a read pair has a hundred alignments each within one 50-kb neighbourhood: one raw molecule of
+    // several hundred entries, in which every entry of the read is scored against every entry of its mate — n_a x n_m evaluations of ten scattered fields each,
+    // half of this kernel's time.  The molecule's entries (position, contig, strand, read, the four counts the score is made of: 24 B) are staged once and every
+    // lane scans them for ITS entry: the same set of mate entries, the same expression evaluated in the same order per pair (lariat.go:599-624 with lmp = 0: adding
+    // 0.0 to a sum that cannot be -0.0 is left out), the maximum of the same values; "first" = no earlier entry of the read in the molecule, as below.
+    {
+        struct MEnt { i64 pos; int32_t rid; uint32_t rd; int32_t s2, spare; };   // s2: twice the entry's own part of a pair's score (below)
+        static_assert(sizeof(MEnt) == 24, "24 bytes per staged entry");
+        MEnt* const me = (MEnt*)lds_raw;
+        // (r06, late) next to the records, the entries' read numbers alone, sixteen bits each: a lane looking for its mate's entries (and for earlier ones of its own
+        // read) reads EIGHT of them per round trip to LDS and fetches a 24-byte record only where the low sixteen bits match — one entry in ten on repeat families, where
+        // the scan of whole records, a dependent LDS read per entry, was two fifths of the kernel on large barcodes
+        constexpr int ME_FIT = (LH_RFA_LDS_BYTES / 26) & ~7;
+#ifdef LH_RFA_ME_CAP   // (test builds: tiles short enough for the suite's molecules to need several)
+        constexpr int ME_CAP = (LH_RFA_ME_CAP < ME_FIT ? LH_RFA_ME_CAP : ME_FIT) & ~7;
+#else
+        constexpr int ME_CAP = ME_FIT;
+#endif
+        static_assert(ME_CAP >= 8 && ME_CAP % 8 == 0 && ME_CAP * 26 <= LH_RFA_LDS_BYTES, "records and read numbers of a tile share lds_raw");
+        uint16_t* const mrd = (uint16_t*)(lds_raw + ME_CAP * 24);   // (16-byte aligned: ME_CAP is a multiple of 8)
+        auto load_ent = [&](int i) {
+            const i64 ca = c_lo + T.plist[i];
+            MEnt e;
+            e.pos = R.pos[ca]; e.rid = R.rid[ca]; e.rd = (uint32_t)T.rdl[i] | (uint32_t)(R.reversed[ca] != 0) << 31;
+            const int sc = R.soft_clipped[ca];
+            e.s2 = R.mismatches[ca] * -4 + R.indels[ca] * -6 - (sc > 0 ? 10 * sc + R.soft_clipped_length[ca] : 0);   // twice (-2 mm - 3 id - 5 sc - 0.5 scl)
+            e.spare = 0;
+            return e;
+        };
+        // (r06) EVERY molecule's entries go through LDS, not only the large ones: the entries of a barcode are cut into tiles of whole molecules (they are contiguous
+        // in position order), a tile is staged once and every lane scans ITS entry's molecule inside it — a handful to a few dozen LDS records where it was as many
+        // dependent reads of ten scattered fields from memory per entry (46 % of the kernel on repeat families, 37 % on 1,000-pair barcodes with a twentieth of their
+        // pairs on them).  A molecule longer than a tile goes through tiles of its own, as in r05.
+        // (r06, late) a pair's score (lariat.go:599-624 with lmp = 0) is the sum of the two entries' own parts — whole and half numbers (-2 per mismatch, -3 per indel,
+        // -5 per clipped end, -0.5 per clipped base), every partial sum exact in a double whatever the order — plus the improper-pair penalty as the LAST addition
+        // when the pair is not proper.  So the largest score over a set of mates is max(half the largest integer sum over the proper ones, half the largest over the
+        // improper ones + penalty) — the same doubles the expression as written yields (x -> x / 2 + penalty does not decrease in x) — and the loop over the mates is
+        // integer work: it was thirty double-precision operations a pair, most of this step on repeat families.
+        auto pair_proper = [&](const MEnt& A, int arev, const MEnt& E) {
+            int pr = 0;
+            if (arev != (int)(E.rd >> 31) && A.rid == E.rid) { const i64 dist = arev ? A.pos - E.pos : E.pos - A.pos; pr = dist >= -35 && dist < 750; }
+            return pr;
+        };
+        constexpr int S2_NONE = -(1 << 30);
+        auto best_of = [&](int bp, int bi) {
+            double best = -1.7976931348623157e308;
+            if (bp != S2_NONE) best = (double)bp * 0.5;
+            if (bi != S2_NONE) { const double x = (double)bi * 0.5 + improper; if (x > best) best = x; }
+            return best;
+        };
+        // entries [j0, j1) of the staged tile against entry A (read lr, mate lrm); the tile's entry j is the molecule's entry jb + j, A is its entry e
+        auto scan_tile = [&](const MEnt& A, int lr, int lrm, int arev, int j0, int j1, int jb, int e, int& bp, int& bi, int& first) {
+            const uint32_t km = (uint32_t)lrm & 0xffffu, ko = (uint32_t)lr & 0xffffu;
+            for (int j8 = j0 & ~7; j8 < j1; j8 += 8) {
+                const u64* const wp = (const u64*)(mrd + j8);
+                const u64 ww[2] = {wp[0], wp[1]};
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const uint32_t id = (uint32_t)(ww[u >> 2] >> ((u & 3) * 16)) & 0xffffu;
+                    const int j = j8 + u;
+                    if ((id == km || id == ko) && j >= j0 && j < j1) {
+                        const MEnt E = me[j];
+                        const int lj = (int)(E.rd & 0x7fffffffu);
+                        if (lj == lrm) {
+                            const int s2 = A.s2 + E.s2;
+                            if (pair_proper(A, arev, E)) bp = bp > s2 ? bp : s2;
+                            else bi = bi > s2 ? bi : s2;
+                        } else if (lj == lr && jb + j < e) first = 0;
+                    }
+                }
+            }
+        };
+        for (int i0 = 0; i0 < NCf;) {
+            const int m0 = T.molraw[i0];
+            const int msz = T.mstart[m0 + 1] - i0;   // (i0 is the first entry of molecule m0)
+            if (msz > ME_CAP) {
+                // a molecule longer than the buffer goes through it in tiles: every entry keeps its maximum so far in sval, "a mate's entry seen" in psum (free until
+                // the counting below) and "first" in firstf
+                const int ms0 = i0;
+                for (int t0 = 0; t0 < msz; t0 += ME_CAP) {
+                    const int tn = msz - t0 < ME_CAP ? msz - t0 : ME_CAP;
+                    WAVE_SYNC();   // the previous tile's entries have been read
+                    for (int j = lane; j < tn; j += 64) { const MEnt E = load_ent(ms0 + t0 + j); me[j] = E; mrd[j] = (uint16_t)(E.rd & 0xffffu); }
+                    WAVE_SYNC();
+                    for (int e0 = 0; e0 < msz; e0 += 64) {
+                        const int e = e0 + lane;
+                        if (e < msz) {
+                            const int i = ms0 + e;
+                            const MEnt A = (e >= t0 && e < t0 + tn) ? me[e - t0] : load_ent(i);
+                            const int lr = (int)(A.rd & 0x7fffffffu), lrm = lr ^ 1, arev = (int)(A.rd >> 31);
+                            double best = -1.7976931348623157e308;
+                            int found = 0, first = 1, bp = S2_NONE, bi = S2_NONE;
+                            if (t0 > 0) { best = T.sval[i]; found = T.psum[i]; first = T.firstf[i]; }
+                            scan_tile(A, lr, lrm, arev, 0, tn, t0, e, bp, bi, first);
+                            if (bp != S2_NONE || bi != S2_NONE) { found = 1; const double x = best_of(bp, bi); if (x > best) best = x; }
+                            if (t0 + tn >= msz) { T.sval[i] = found ? best : R.lap[c_lo + T.plist[i]]; T.firstf[i] = first; }
+                            else { T.sval[i] = best; T.psum[i] = found; T.firstf[i] = first; }
+                        }
+                    }
+                }
+                i0 += msz;
+                continue;
+            }
+            // whole molecules from i0 on: up to the start of the molecule that holds entry i0 + ME_CAP
+            int i1 = NCf;
+            if (i0 + ME_CAP < NCf) i1 = T.mstart[T.molraw[i0 + ME_CAP]];
+            const int tn = i1 - i0;
+            WAVE_SYNC();   // the previous tile's entries have been read
+            for (int j = lane; j < tn; j += 64) { const MEnt E = load_ent(i0 + j); me[j] = E; mrd[j] = (uint16_t)(E.rd & 0xffffu); }
+            WAVE_SYNC();
+            RFA_PROF(17)
+            for (int e0 = 0; e0 < tn; e0 += 64) {
+                const int e = e0 + lane;
+                if (e < tn) {
+                    const int i = i0 + e, m = T.molraw[i];
+                    const int j0 = T.mstart[m] - i0, j1 = T.mstart[m + 1] - i0;
+                    const MEnt A = me[e];
+                    const int lr = (int)(A.rd & 0x7fffffffu), lrm = lr ^ 1, arev = (int)(A.rd >> 31);
+                    int first = 1, bp = S2_NONE, bi = S2_NONE;
+                    scan_tile(A, lr, lrm, arev, j0, j1, 0, e, bp, bi, first);
+                    T.sval[i] = bp != S2_NONE || bi != S2_NONE ? best_of(bp, bi) : R.lap[c_lo + T.plist[i]];
+                    T.firstf[i] = first;
+                }
+            }
+            RFA_PROF(18)
+            i0 = i1;
+        }
+        WAVE_SYNC();
+    }
+    int nfirst = 0, nactive = 0;
+    for (int base = 0; base < NCf; base += 64) {
+        int i = base + lane, first = 0, isact = 0;
+        const int pre = i < NCf ? T.firstf[i] : -1;
+        if (i < NCf && pre >= 0) { first = pre; isact = S.active[c_lo + T.plist[i]] != 0; }
+        u64 mf = __ballot(first), ma = __ballot(isact);
+        if (i < NCf) { T.psum[i] = nfirst + lanes_below(mf, lane); T.actc[i] = nactive + lanes_below(ma, lane); }
+        nfirst += __popcll(mf); nactive += __popcll(ma);
+    }
+    if (lane == 0) { T.psum[NCf] = nfirst; T.actc[NCf] = nactive; }
+    WAVE_SYNC();
+}
+
+// scrapMolecules (lariat.go:1061-1086): the molecules with an active alignment, renumbered 0 .. M-1.
+// Reads: T.mstart, T.actc, T.psum.  Writes and leaves: T.newid [Mraw], T.seg0 / T.seg1 [M], H.nbest / H.aoff [M], H.alen = 0 (the small instance: for the first LH_RFA_SM_M only).
+// Returns M; whether the tables hold that many is the loop's to decide, before anything is written that the next launch does not write again.  lds_raw: only H.
+template <int SMALL, typename HOT>
+__device__ __forceinline__ int rfa_scrap_molecules(const RfaTab& T, const HOT& H, const RfaBc& B, int lane) {
+    const int Mraw = B.Mraw;
+    int M = 0;
+    // ---- scrapMolecules: keep molecules with an active alignment, renumber ----
+    int ao = 0;
+    for (int base = 0; base < Mraw; base += 64) {
+        int m = base + lane;
+        int keep = m < Mraw && T.actc[T.mstart[m + 1]] - T.actc[T.mstart[m]] > 0;
+        int nr = keep ? T.psum[T.mstart[m + 1]] - T.psum[T.mstart[m]] : 0;
+        u64 mk = __ballot(keep);
+        int id = M + lanes_below(mk, lane);
+        int inc = wave_scan_add_i32(nr);
+        if (keep) {
+            T.newid[m] = id; T.seg0[id] = T.mstart[m]; T.seg1[id] = T.mstart[m + 1];
+            if (!SMALL || id < LH_RFA_SM_M) { H.nbest[id] = nr; H.aoff[id] = ao + inc - nr; H.alen[id] = 0; }   // (small: the on-chip tables end at LH_RFA_SM_M; more molecules: turned away below)
+        }
+        else if (m < Mraw) T.newid[m] = -1;
+        M += __popcll(mk);
+        ao += wave_readlane(inc, 63);
+    }
+    WAVE_SYNC();
+    return M;
+}
+
+// ---- calculateLogMoleculePenalty (lariat.go:1061-1086) ----
+// Every term of dnaLength is an integer-valued double far below 2^53, so the sum is exact in any order: the lanes share a
+// molecule's alignments (it was one lane walking all of them, 16 % of the kernel's time), the wave adds up.
+// Reads: H.alen / H.aoff / H.mflag / H.act_store (the last phase to: the small instance's range of lds_raw is free after it).  Writes: shd[0].  Returns the penalty
+// (0 for a barcode without molecules).
+template <typename HOT>
+__device__ __forceinline__ double rfa_molecule_penalty(const DCand& R, const HOT& H, const RfaBc& B, int lane, double* shd, double genome_length) {
+    const i64 c_lo = B.c_lo;
+    const int M = B.M;
+    {
+        double part = 0.0;
+        if (B.do_rfa && M > 0) {
+            for (int m = 0; m < M; ++m) {
+                const int al = H.alen[m], ao = H.aoff[m];
+                if (H.mflag[m]) {
+                    i64 smallest = 0x7fffffffffffffffll, biggest = -1;
+                    for (int k = lane; k < al; k += 64) {
+                        i64 p = R.pos[c_lo + H.act_store[ao + k]];
+                        if (p > biggest) biggest = p;
+                        if (p < smallest) smallest = p;
+                    }
+                    for (int msk = 32; msk >= 1; msk >>= 1) {
+                        const i64 ob = shfl_xor_i64(biggest, msk), os = shfl_xor_i64(smallest, msk);
+                        if (ob > biggest) biggest = ob;
+                        if (os < smallest) smallest = os;
+                    }
+                    if (lane == 0 && biggest >= smallest) part += (double)(biggest - smallest) + 1000.0;
+                } else {
+                    for (int k = lane; k < al; k += 64) {
+                        i64 g = c_lo + H.act_store[ao + k];
+                        part += (double)(R.aend[g] - R.pos[g]) * 2.0;
+                    }
+                }
+            }
+        }
+        for (int msk = 32; msk >= 1; msk >>= 1) part += __shfl_xor(part, msk);
+        if (lane == 0) shd[0] = (B.do_rfa && M > 0) ? log10((1000.0 + part) / genome_length * 0.05) : 0.0;
+    }
+    WAVE_SYNC();
+    return shd[0];
+}
+
+// Link active mates (estimateMapQualities, lariat.go:892-900), for all reads before any scoring that reads mate links.
+// Reads: S.active.  Writes and leaves: S.active_idx [the barcode's reads], S.mate of every active alignment.  No table of the barcode, no lds_raw.
+__device__ __forceinline__ void rfa_link_mates(const DCand& R, const DInf& S, const RfaBc& B, int lane) {
+    const int r0 = B.r0, nR = B.nR;
+    // ---- per read: link active mates (lariat.go:892-900).  Done for all reads before any scoring that reads mate links. ----
+    for (int r = lane; r < nR; r += 64) {
+        i64 act = -1;
+        for (i64 a = R.cand_off[r0 + r]; a < R.cand_off[r0 + r + 1]; ++a) if (R.in_filtered[a] && S.active[a]) act = a;
+        S.active_idx[r0 + r] = act;
+    }
+    WAVE_SYNC();
+    for (int r = lane; r < nR; r += 64) {
+        i64 a = S.active_idx[r0 + r], m = S.active_idx[r0 + (r ^ 1)];
+        S.mate[a] = m;
+    }
+    WAVE_SYNC();
+}
+
+// The reads with many (alignment, mate alignment) combinations (estimateMapQualities, lariat.go:887-990) are listed for k_rfa_mq_w, with the barcode, whose molecule penalty they need.
+// Writes: bc_lmp[bc], hr_list / *hr_count.  No table of the barcode, no lds_raw.
+__device__ __forceinline__ void rfa_list_heavy_reads(const DCand& R, const RfaBc& B, int lane, double lmp, double* bc_lmp, int32_t* hr_list, int32_t* hr_count) {
+    const int r0 = B.r0, nR = B.nR;
+    if (lane == 0) bc_lmp[B.bc] = lmp;
+    for (int rb_ = 0; rb_ < nR; rb_ += 64) {
+        const int r = rb_ + lane;
+        int hv = 0;
+        if (r < nR) hv = (R.cand_off[r0 + r + 1] - R.cand_off[r0 + r]) * (R.cand_off[r0 + (r ^ 1) + 1] - R.cand_off[r0 + (r ^ 1)]) > LH_RFA_MAPQ_WAVE;
+        const u64 mh = __ballot(hv);
+        if (mh) {
+            int basep = 0;
+            if (lane == 0) basep = atomicAdd(hr_count, (int32_t)__popcll(mh));
+            basep = wave_readlane(basep, 0);
+            if (hv) { const int at = basep + lanes_below(mh, lane); hr_list[2 * at] = r0 + r; hr_list[2 * at + 1] = B.bc; }
+        }
+    }
+    WAVE_SYNC();
+}
+
+// a lane's LH_MAPQ_TOP best scores, largest first, lane-strided in LDS (entry k of the lane at top[k * 64 + lane]); ntop: how many it holds
+__device__ __forceinline__ void rfa_top_push(double* top, int lane, int& ntop, double v) {
+    int k = ntop < LH_MAPQ_TOP ? ntop : LH_MAPQ_TOP;
+    if (ntop < LH_MAPQ_TOP || v > top[(LH_MAPQ_TOP - 1) * 64 + lane]) {
+        if (ntop < LH_MAPQ_TOP) ntop++; else k = LH_MAPQ_TOP - 1;
+        while (k > 0 && top[(k - 1) * 64 + lane] < v) { top[k * 64 + lane] = top[(k - 1) * 64 + lane]; k--; }
+        top[k * 64 + lane] = v;
+    }
+}
+// estimateMapQualities (lariat.go:887-990) for the reads with few (alignment, mate alignment) combinations, a lane per read (the others: k_rfa_mq_w).
+// Reads: S.active, S.active_idx, S.active_molecule, S.sum_move, S.mate.  Writes: S.mapq, S.mate (of the second-best alignment), S.second_best_idx / _score, S.as_score.
+// lds_raw: scratch, all of it (the lanes' top scores) — every phase that kept something there is over.
+__device__ __forceinline__ void rfa_mapq_lane(const DCand& R, const DInf& S, const RfaBc& B, int lane, double improper, double lmp, const i64* cen_start, const i64* cen_end, uint8_t* lds_raw) {
+    const int r0 = B.r0, nR = B.nR;
+    for (int r = lane; r < nR; r += 64) {
+        int gr = r0 + r, gm = r0 + (r ^ 1);
+        i64 a0 = R.cand_off[gr], a1 = R.cand_off[gr + 1], m0 = R.cand_off[gm], m1 = R.cand_off[gm + 1];
+        if ((a1 - a0) * (m1 - m0) > LH_RFA_MAPQ_WAVE) continue;
+        double* const top = (double*)lds_raw;   // the read's 15 best scores, lane-strided in LDS (the phases that staged things there are over): no scratch
+        int ntop = 0;
+        // pseudo-count entry (appendPsuedocountAlignmentScore): first filtered alignment of the read + best single mate
+        i64 first = -1;
+        for (i64 a = a0; a < a1; ++a) if (R.in_filtered[a]) { first = a; break; }
+        double bestSingle = -1.7976931348623157e308;
+        for (i64 m = m0; m < m1; ++m) {
+            if (!R.in_filtered[m]) continue;
+            double s = dev_score_aln(R, S, improper, -1, m, lmp);
+            if (s > bestSingle) bestSingle = s;
+        }
+        double pseudo = bestSingle + dev_pseudo_score(R, first, lmp);
+        rfa_top_push(top, lane, ntop, pseudo);
+        for (i64 a = a0; a < a1; ++a) {   // best pair score of every alignment
+            if (!R.in_filtered[a]) continue;
+            double best = -1.7976931348623157e308;
+            for (i64 m = m0; m < m1; ++m) {
+                if (!R.in_filtered[m]) continue;
+                double s = dev_score_aln(R, S, improper, a, m, lmp);
+                if (s > best) best = s;
+            }
+            rfa_top_push(top, lane, ntop, best);
+        }
+        // second best (lariat.go:917-943); sets mate_alignment of the inactive alignment it selects
+        double sb_raw = pseudo, sb_lp = -1000.0;
+        i64 sb_aln = -1;
+        for (i64 a = a0; a < a1; ++a) {
+            if (!R.in_filtered[a] || S.active[a]) continue;
+            for (i64 m = m0; m < m1; ++m) {
+                if (!R.in_filtered[m]) continue;
+                double s = dev_score_aln(R, S, improper, a, m, lmp);
+                if (s > sb_lp) { sb_lp = s; sb_raw = dev_score_aln(R, S, improper, a, m, 0.0); sb_aln = a; S.mate[a] = m; }
+            }
+        }
+        i64 act = S.active_idx[gr];
+        S.second_best_idx[gr] = sb_aln; S.second_best_score[gr] = sb_raw;
+        S.as_score[gr] = dev_score_aln(R, S, improper, act, S.mate[act], 0.0);
+        double total = 0;
+        for (int k = 0; k < ntop; ++k) total += dev_mapq_pow10(top[k * 64 + lane]);
+        for (i64 a = a0; a < a1; ++a) {
+            if (!R.in_filtered[a]) continue;
+            S.mapq[a] = dev_mapq(dev_score_aln(R, S, improper, a, S.mate[a], lmp), total, S.sum_move[a], dev_in_centromere(R, cen_start, cen_end, a));
+        }
+    }
+    WAVE_SYNC();
+}
+
+
+
 // (r13) SMALL = 1: the instance for the barcodes k_rfa_order lists as small (LH_RFA_SM_*).  Its hot tables (RfaHot) live in LDS from scrapMolecules to the molecule
 // penalty, behind fastScore's staging; the branches only larger barcodes take (grouping through LDS atomics, contig lists longer than the sort buffer, the contig
 // tables in the slab) are not compiled into it.  A barcode beyond the caps, or with more than LH_RFA_SM_M molecules once they are counted, is appended to ovf_list —
@@ -713,8 +1466,6 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
     // staging, [RFA_HOT_OFF, RFA_HOT_OFF + RFA_HOT_BYTES): written from scrapMolecules on — markBest's tiles are done by then —, last read by the molecule penalty —
     // the top-15 scores come after it.  Nothing else touches lds_raw in between.
     __shared__ __attribute__((aligned(16))) uint8_t lds_raw[LH_RFA_LDS_BYTES];
-    i64* const spos = (i64*)lds_raw;                                               // position sort
-    int32_t* const sidx = (int32_t*)(lds_raw + 8 * LH_RFA_SORT_LDS);
     int32_t* const sLr = (int32_t*)lds_raw;                                        // fastScore source staging
     int32_t* const sFl = sLr + LH_RFA_SRC_CHUNK;
     double* const sLap = (double*)(sFl + LH_RFA_SRC_CHUNK);
@@ -764,22 +1515,20 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         // ---- slab carve (sizes depend on NC, nR) ----
         size_t so = 0;
         RfaTab T;
-#define CARVE(ptr, type, count) { so = (so + 7) & ~(size_t)7; T.ptr = (type*)(slab + so); so += sizeof(type) * (size_t)(count); }
         int ncmax = ix.n_contigs + 2;
         if constexpr (SMALL) {
             // the small instance carves for its caps, not for the barcode: every table at a fixed place of the slab — one base and constants, where forty table
             // addresses held across the whole program spilled (k_rfa_order lists a barcode as small only where a slab holds this carve: rfa_small_bytes)
             constexpr int NC = LH_RFA_SM_NC, nR = LH_RFA_SM_NR, ncmax = LH_RFA_NCONT_LDS, hbits = rfa_hbits_c(LH_RFA_SM_NR);
-            LH_RFA_CARVE_LIST(CARVE)
+            LH_RFA_CARVE_LIST(LH_RFA_CARVE)
         } else {
             int hbits = 6;
             while ((1 << hbits) < 2 * nR) ++hbits;
-            LH_RFA_CARVE_LIST(CARVE)
+            LH_RFA_CARVE_LIST(LH_RFA_CARVE)
         }
         so = (so + 7) & ~(size_t)7;
         T.bestT = (int32_t*)(slab + so);
         size_t best_cap = ((size_t)slab_bytes > so) ? ((size_t)slab_bytes - so) / 4 : 0;
-#undef CARVE
         if (so > (size_t)slab_bytes) RFA_OVERFLOW()   // barcode too large for the slab
         typedef typename RfaHotWord<SMALL>::type hot_t;
         RfaHot<hot_t> H;
@@ -799,380 +1548,17 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         // one candidate in four to sixteen starts a molecule, and a barcode sent on waits for one of fewer waves; 4,000 x 100 pairs 108 -> 155 ms, 1,000 x 400 pairs 0.44 -> 1.1 s)
         // ---- positions: filtered candidates grouped by contig in first-seen order, candidate order inside a contig ----
         int ncont = 0, NCf = 0;
-        if (!SMALL && ncmax <= LH_RFA_NCONT_LDS && NC > 256) {
-            // (r06) a large barcode, a contig table that fits LDS: the contigs' first-seen order from one atomic minimum per candidate (the smallest candidate index
-            // that names the contig), slot sizes from one atomic add, and the stable placement from the lanes that share a slot — found with one ballot per bit of
-            // the slot number, not one loop turn per slot present in the chunk (a read on repeat families names thirty contigs: the three passes were a sixth of the
-            // kernel for a barcode of 10,000 candidates, most of it loop turns and a 36-deep search per candidate).
-            int32_t* const fs = (int32_t*)lds_raw;                          // [ncmax] by contig + 1: its first candidate, then its slot
-            int32_t* const scnt2 = (int32_t*)lds_raw + LH_RFA_NCONT_LDS;    // [ncont] slot sizes, then running write positions
-            for (int x = lane; x < ncmax; x += 64) fs[x] = 0x7fffffff;
-            WAVE_SYNC();
-            for (int a = lane; a < NC; a += 64) if (R.in_filtered[c_lo + a]) atomicMin(&fs[R.rid[c_lo + a] + 1], a);   // (+ 1: a read without a region has a placeholder on contig -1, a group of its own)
-            WAVE_SYNC();
-            // the contigs present, in the order of their first candidates: rank by counting (a few dozen of them)
-            for (int base = 0; base < ncmax; base += 64) {
-                const int x = base + lane;
-                const int f = x < ncmax ? fs[x] : 0x7fffffff;
-                int rank = -1;
-                if (f != 0x7fffffff) { rank = 0; for (int y = 0; y < ncmax; ++y) rank += fs[y] < f; }
-                const u64 pm = __ballot(rank >= 0);
-                if (rank >= 0) { T.seen_rid[rank] = x; T.ccnt[x] = rank; }
-                ncont += __popcll(pm);
-            }
-            WAVE_SYNC();
-            for (int x = lane; x < ncmax; x += 64) fs[x] = fs[x] != 0x7fffffff ? T.ccnt[x] : -1;   // contig -> slot
-            for (int k = lane; k < ncont; k += 64) scnt2[k] = 0;
-            WAVE_SYNC();
-            for (int a = lane; a < NC; a += 64) {
-                const int k = R.in_filtered[c_lo + a] ? fs[R.rid[c_lo + a] + 1] : -1;
-                T.kidx[a] = k;
-                if (k >= 0) atomicAdd(&scnt2[k], 1);
-            }
-            WAVE_SYNC();
-            for (int base = 0; base < ncont; base += 64) {   // slot offsets; scnt2 becomes the running write position
-                const int k = base + lane;
-                const int c = k < ncont ? scnt2[k] : 0;
-                const int inc = wave_scan_add_i32(c);
-                EMU_SYNC();
-                if (k < ncont) { T.coff[k] = NCf + inc - c; scnt2[k] = NCf + inc - c; }
-                NCf += wave_readlane(inc, 63);
-            }
-            if (lane == 0) T.coff[ncont] = NCf;
-            WAVE_SYNC();
-            int kbits = 1;
-            while ((1 << kbits) < ncont) ++kbits;
-            for (int base = 0; base < NC; base += 64) {   // stable placement: candidate order inside a slot
-                const int a = base + lane;
-                const int k = a < NC ? T.kidx[a] : -1;
-                const int valid = k >= 0;
-                u64 peers = __ballot(valid);
-                for (int b = 0; b < kbits; ++b) { const u64 bb = __ballot(valid && ((k >> b) & 1)); peers &= ((k >> b) & 1) ? bb : ~bb; }
-                const int at = valid ? scnt2[k] : 0;
-                EMU_SYNC();
-                if (valid) {
-                    T.plist[at + lanes_below(peers, lane)] = a;
-                    if (lanes_below(peers, lane) == 0) scnt2[k] = at + __popcll(peers);
-                }
-                WAVE_SYNC();
-            }
-        } else {
-        // pass A: contig slot of every candidate (first-seen numbering) and the slot sizes
-        int32_t* const seen = SMALL || ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw : T.seen_rid;
-        int32_t* const scnt = SMALL || ncmax <= LH_RFA_NCONT_LDS ? (int32_t*)lds_raw + LH_RFA_NCONT_LDS : T.ccnt;
-        for (int base = 0; base < NC; base += 64) {
-            int a = base + lane;
-            int valid = a < NC && R.in_filtered[c_lo + a];
-            int rid = valid ? R.rid[c_lo + a] : 0;
-            int k = -1;
-            if (valid) for (int j = ncont - 1; j >= 0; --j) if (seen[j] == rid) { k = j; break; }
-            u64 un = __ballot(valid && k < 0);
-            while (un) {   // contigs met for the first time, in candidate order
-                int leader = __ffsll((unsigned long long)un) - 1;
-                int lrid = wave_readlane(rid, leader);
-                if (lane == 0) { seen[ncont] = lrid; scnt[ncont] = 0; }
-                if (valid && k < 0 && rid == lrid) k = ncont;
-                ncont++;
-                un = __ballot(valid && k < 0);
-            }
-            WAVE_SYNC();
-            if (a < NC) T.kidx[a] = valid ? k : -1;
-            u64 rem = __ballot(valid);
-            while (rem) {
-                int kk = wave_readlane(k, __ffsll((unsigned long long)rem) - 1);
-                u64 m = __ballot(valid && k == kk);
-                if (lane == 0) scnt[kk] += __popcll(m);
-                rem &= ~m;
-            }
-            WAVE_SYNC();
-        }
-        for (int base = 0; base < ncont; base += 64) {   // slot offsets; scnt becomes the running write position
-            int k = base + lane;
-            int c = k < ncont ? scnt[k] : 0;
-            int inc = wave_scan_add_i32(c);
-            EMU_SYNC();
-            if (k < ncont) { T.coff[k] = NCf + inc - c; scnt[k] = NCf + inc - c; }
-            NCf += wave_readlane(inc, 63);
-        }
-        if (lane == 0) T.coff[ncont] = NCf;
-        WAVE_SYNC();
-        // pass B: stable placement
-        for (int base = 0; base < NC; base += 64) {
-            int a = base + lane;
-            int k = a < NC ? T.kidx[a] : -1;
-            int valid = k >= 0;
-            u64 rem = __ballot(valid);
-            while (rem) {
-                int kk = wave_readlane(k, __ffsll((unsigned long long)rem) - 1);
-                u64 m = __ballot(valid && k == kk);
-                int at = scnt[kk];
-                EMU_SYNC();
-                if (valid && k == kk) T.plist[at + lanes_below(m, lane)] = a;
-                if (lane == 0) scnt[kk] = at + __popcll(m);
-                EMU_SYNC();
-                rem &= ~m;
-            }
-        }
-        WAVE_SYNC();
-        }
+        { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, 0, ncont, NCf, 0, 0}; NCf = rfa_group_contigs<SMALL>(R, T, B, lane, lds_raw, &ncont); }
         RFA_PROF(3)
         RFA_FENCE()
-        // sort.Sort(ByPosition) per contig (lariat.go:1545-1547), one lane per contig; keys staged in LDS when they fit
-        if (NCf <= LH_RFA_SORT_LDS && ncont <= 8) {
-            // Few contigs: the wave sorts one contig at a time by ranking (every lane counts the smaller keys of its elements).
-            // Go's sort is unstable, but with all keys different there is only one sorted order; a contig with two equal
-            // positions is sorted again by the serial restatement of Go's algorithm.
-            for (int i = lane; i < NCf; i += 64) { sidx[i] = T.plist[i]; spos[i] = R.pos[c_lo + T.plist[i]]; }
-            WAVE_SYNC();
-            for (int k = 0; k < ncont; ++k) {
-                int b0 = T.coff[k], n = T.coff[k + 1] - b0;
-                i64* kp = spos + b0;
-                int32_t* ip = sidx + b0;
-                int tie = 0;
-                for (int e = lane; e < n; e += 64) {
-                    i64 key = kp[e];
-                    int rank = 0;
-                    for (int j = 0; j < n; ++j) { i64 kj = kp[j]; rank += kj < key; tie |= (kj == key) & (j != e); }
-                    T.plist[b0 + rank] = ip[e];
-                }
-                if (__any(tie)) {
-                    WAVE_SYNC();
-                    if (lane == 0)
-                        dev_gosort(n, [&](int i, int j) { return kp[i] < kp[j]; },
-                                   [&](int i, int j) { i64 t = kp[i]; kp[i] = kp[j]; kp[j] = t; int u = ip[i]; ip[i] = ip[j]; ip[j] = u; }, T.gstk + lane, 64);
-                    WAVE_SYNC();
-                    for (int e = lane; e < n; e += 64) T.plist[b0 + e] = ip[e];
-                }
-            }
-        } else if (SMALL || NCf <= LH_RFA_SORT_LDS) {
-            for (int i = lane; i < NCf; i += 64) { sidx[i] = T.plist[i]; spos[i] = R.pos[c_lo + T.plist[i]]; }
-            WAVE_SYNC();
-            for (int k = lane; k < ncont; k += 64) {
-                int b0 = T.coff[k], n = T.coff[k + 1] - b0;
-                i64* kp = spos + b0;
-                int32_t* ip = sidx + b0;
-                dev_gosort(n, [&](int i, int j) { return kp[i] < kp[j]; },
-                           [&](int i, int j) { i64 t = kp[i]; kp[i] = kp[j]; kp[j] = t; int u = ip[i]; ip[i] = ip[j]; ip[j] = u; }, T.gstk + lane, 64);
-            }
-            WAVE_SYNC();
-            for (int i = lane; i < NCf; i += 64) T.plist[i] = sidx[i];
-        } else {
-            // More candidates than the LDS buffer holds (a barcode on repeat families has thousands; the reader's cap is 30,000 pairs).  Contig by contig (r05):
-            // a contig's list that fits the buffer is staged there and sorted by ranking, as above — with all keys different there is only one sorted order; two
-            // equal positions: Go's algorithm, serially, in LDS —; a longer one is sorted in memory with the ranges of Go's quickSort spread over the lanes
-            // (lh_sort.h: wave_gosort; keys next to the list in sval, free until the molecules are scored; molraw / rdl / firstf hold the queue of ranges).
-            // (All of them at once in memory, the r04 form, was 10 % of the kernel on the repeat input: the first levels of every quickSort are one lane's.)
-            i64* const kpg = (i64*)T.sval;
-            int32_t* const pl = T.plist;
-            for (int k = 0; k < ncont; ++k) {
-                const int b0 = T.coff[k], n = T.coff[k + 1] - b0;
-#ifdef LH_RA_HIST
-                if (lane == 0) { atomicAdd(&lh_rfa_hist2[0], 1ull); atomicMax(&lh_rfa_hist2[1], (unsigned long long)n); if (n > LH_RFA_SORT_LDS) atomicAdd(&lh_rfa_hist2[2], 1ull); if (n > LH_RFA_LDS_BYTES / 4) atomicAdd(&lh_rfa_hist2[3], 1ull); atomicAdd(&lh_rfa_hist2[4], (unsigned long long)n * n); }
-#endif
-                if (n < 2) continue;
-                if (n > 64 && n < (1 << 20)) {
-                    // (r06) a list of more than a wave's worth is put in order by a sorting NETWORK on packed words ((position - smallest) << 20 | place in the list), in the
-                    // slab (sval, free until the molecules are scored) — instead of by ranking (every lane counting the smaller keys
-                    // of its elements: n^2 / 64 steps; 2,000 entries of one contig, common for a 1,000-pair barcode with a twentieth of its pairs on repeat families, were
-                    // 62,000 steps a list and the position sorts a third of the kernel).  With all keys different there is only one sorted order, whatever the algorithm;
-                    // two equal positions (adjacent after the sort): Go's algorithm on the list as it was, below.
-                    u64* const bk = (u64*)kpg + b0;   // (always in the slab: a pointer that is LDS for short lists and memory for long ones is a flat one — that form faulted on the device, and this one measured faster)
-                    WAVE_SYNC();   // the previous contig's keys have been read
-                    RFA_PROF(1)
-                    // the positions, gathered ONCE (eight independent reads a lane in flight) into the slab next to the list, and the smallest of them
-                    i64 mn = 0x7fffffffffffffffll;
-                    for (int i0 = lane; i0 < n; i0 += 64 * 8) {
-                        int ca[8];
-                        i64 x[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) ca[u] = i0 + 64 * u < n ? pl[b0 + i0 + 64 * u] : -1;
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) x[u] = ca[u] >= 0 ? R.pos[c_lo + ca[u]] : 0x7fffffffffffffffll;
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) { if (ca[u] >= 0) bk[i0 + 64 * u] = (u64)x[u]; mn = mn < x[u] ? mn : x[u]; }
-                    }
-                    mn = wave_min_i64(mn);
-                    RFA_PROF(22)
-                    if (n <= LH_RFA_NET_BLOCK) {
-                        // up to 1,024 keys: the network runs in LDS (a pass is a round trip to LDS, not to the slab: thirty lists a barcode, 36 - 55 passes each) and its result is
-                        // copied to the slab, where everything that follows reads it — through its own pointer, never one that is LDS for some lists and memory for others
-                        u64* const lk = (u64*)lds_raw;
-                        for (int i = lane; i < n; i += 64) lk[i] = (u64)((i64)bk[i] - mn) << 20 | (u64)i;
-                        WAVE_SYNC();
-                        RFA_PROF(23)
-                        wave_bitonic_u64(lk, n, lane);
-                        for (int i = lane; i < n; i += 64) bk[i] = lk[i];
-                        WAVE_SYNC();
-                    } else {
-                        // longer: the network block by block through LDS, a few passes over the list in the slab between them (lh_sort.h)
-                        for (int i = lane; i < n; i += 64) bk[i] = (u64)((i64)bk[i] - mn) << 20 | (u64)i;
-                        WAVE_SYNC();
-                        RFA_PROF(23)
-                        wave_bitonic_u64_blocks<LH_RFA_NET_BLOCK>(bk, n, (u64*)lds_raw, lane);
-                    }
-                    RFA_PROF(19)
-                    int tie = 0;
-                    for (int e = lane; e < n; e += 64) {
-                        const u64 w = bk[e];
-                        if (e + 1 < n) tie |= (bk[e + 1] >> 20) == (w >> 20);
-                        T.molraw[b0 + e] = pl[b0 + (int)(w & 0xfffffu)];
-                    }
-                    const int tied = __any(tie);
-#ifdef LH_RA_HIST
-                    if (tied && lane == 0) atomicAdd(&lh_rfa_hist2[5], 1ull);
-#endif
-                    WAVE_SYNC();
-                    if (!tied) {
-                        for (int e = lane; e < n; e += 64) pl[b0 + e] = T.molraw[b0 + e];
-                        WAVE_SYNC();
-                        RFA_PROF(20)
-                        continue;
-                    }
-                    RFA_PROF(20)
-                    if (n <= LH_RFA_TIE_LDS) {
-                        // Two equal positions: Go's algorithm (its ranges spread over the lanes) on the list AS IT WAS — but on one word per entry in LDS: Less only asks which of two
-                        // positions is smaller, so a position's dense RANK (from the network's order: equal positions share one) answers for it, and (rank << 12 | place) is a
-                        // 32-bit word that a Swap moves whole.  Up to 2,304 entries instead of 768 (12 bytes each: position and place), and lists of 800 - 2,300 entries — two reads
-                        // at the same offset of a 300-bp family tie on EVERY copy — were sorted in memory, two dependent reads per comparison.
-                        int carry = 0;
-                        for (int e0 = 0; e0 < n; e0 += 64) {
-                            const int e = e0 + lane;
-                            int fl = 0;
-                            u64 w = 0;
-                            if (e < n) { w = bk[e]; fl = e > 0 && (bk[e - 1] >> 20) != (w >> 20); }
-                            const int rk = carry + wave_scan_add_i32(fl);
-                            if (e < n) T.rdl[b0 + (int)(w & 0xfffffu)] = rk;   // (rdl: free until inferMolecules)
-                            carry = wave_readlane(rk, 63);
-                        }
-                        WAVE_SYNC();
-                        uint32_t* const g32 = (uint32_t*)lds_raw;
-                        for (int i = lane; i < n; i += 64) g32[i] = (uint32_t)T.rdl[b0 + i] << 12 | (uint32_t)i;
-                        if (lane == 0) { shi[6] = 0; shi[7] = n; }
-                        WAVE_SYNC();
-                        wave_gosort(1, shi + 6, [&](int i, int j) { return (g32[i] >> 12) < (g32[j] >> 12); },
-                                    [&](int i, int j) { const uint32_t t = g32[i]; g32[i] = g32[j]; g32[j] = t; }, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);   // (molc, ppos: set after the sorts)
-                        WAVE_SYNC();
-                        for (int e = lane; e < n; e += 64) T.molc[b0 + e] = pl[b0 + (int)(g32[e] & 0xfffu)];   // (molc: set after the sorts)
-                        WAVE_SYNC();
-                        for (int e = lane; e < n; e += 64) pl[b0 + e] = T.molc[b0 + e];
-                        WAVE_SYNC();
-                        RFA_PROF(21)
-                        continue;
-                    }
-                    {
-                        // (r06, late) longer still — several thousand entries on one contig, a 400-pair barcode on repeat families — and two equal positions: Go's algorithm
-                        // on (rank << 20 | place) words in the slab, where the network's keys were: its long ranges are partitioned by the whole wave there (coalesced passes),
-                        // and every range of up to a block's length is sorted in LDS with the depth the long sort has left it.  (It was Go's algorithm on positions and
-                        // places in memory, a lane a range: a sixth of the kernel on such barcodes.)
-                        int carry = 0;
-                        for (int e0 = 0; e0 < n; e0 += 64) {
-                            const int e = e0 + lane;
-                            int fl = 0;
-                            u64 w = 0;
-                            if (e < n) { w = bk[e]; fl = e > 0 && (bk[e - 1] >> 20) != (w >> 20); }
-                            const int rk = carry + wave_scan_add_i32(fl);
-                            if (e < n) T.rdl[b0 + (int)(w & 0xfffffu)] = rk;
-                            carry = wave_readlane(rk, 63);
-                        }
-                        WAVE_SYNC();
-                        for (int i = lane; i < n; i += 64) bk[i] = (u64)(uint32_t)T.rdl[b0 + i] << 20 | (u64)i;
-                        WAVE_SYNC();
-                        auto less_g = [&](int i, int j) { return (bk[i] >> 20) < (bk[j] >> 20); };
-                        auto swp_g = [&](int i, int j) { const u64 t = bk[i]; bk[i] = bk[j]; bk[j] = t; };
-                        const int nq = wave_gosort_split(0, n, LH_RFA_NET_BLOCK, less_g, swp_g, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);
-                        const int qo = n / 16 + 64;   // (the ranges of the sorts in LDS wait behind those of the long one: fewer than n / 25 of the latter, at most a block's length of the former)
-                        u64* const lk = (u64*)lds_raw;
-                        for (int q = 0; q < nq; ++q) {
-                            const int a = T.molraw[q], len = T.rdl[q] - a, d = T.firstf[q];
-                            if (len < 2) continue;
-                            if (len > LH_RFA_NET_BLOCK) {   // (its depth used up before it was short: Go's heap sort, where it lies)
-                                WAVE_SYNC();
-                                if (lane == 0) { shi[6] = a; shi[7] = a + len; }
-                                WAVE_SYNC();
-                                wave_gosort(1, shi + 6, less_g, swp_g, T.molraw + qo, T.rdl + qo, T.firstf + qo, T.molc, T.ppos, d);
-                                WAVE_SYNC();
-                                continue;
-                            }
-                            WAVE_SYNC();
-                            for (int i = lane; i < len; i += 64) lk[i] = bk[a + i];
-                            if (lane == 0) { shi[6] = 0; shi[7] = len; }
-                            WAVE_SYNC();
-                            wave_gosort(1, shi + 6, [&](int i, int j) { return (lk[i] >> 20) < (lk[j] >> 20); }, [&](int i, int j) { const u64 t = lk[i]; lk[i] = lk[j]; lk[j] = t; },
-                                        T.molraw + qo, T.rdl + qo, T.firstf + qo, T.molc, T.ppos, d);
-                            WAVE_SYNC();
-                            for (int i = lane; i < len; i += 64) bk[a + i] = lk[i];
-                        }
-                        WAVE_SYNC();
-                        for (int e = lane; e < n; e += 64) T.molc[b0 + e] = pl[b0 + (int)(bk[e] & 0xfffffu)];
-                        WAVE_SYNC();
-                        for (int e = lane; e < n; e += 64) pl[b0 + e] = T.molc[b0 + e];
-                        WAVE_SYNC();
-                        RFA_PROF(21)
-                        continue;
-                    }
-                }
-                if (n > LH_RFA_SORT_LDS) {
-                    for (int i = lane; i < n; i += 64) kpg[b0 + i] = R.pos[c_lo + pl[b0 + i]];
-                    WAVE_SYNC();
-                    wave_gosort(1, T.coff + k, [&](int i, int j) { return kpg[i] < kpg[j]; },
-                                [&](int i, int j) { i64 t = kpg[i]; kpg[i] = kpg[j]; kpg[j] = t; int u = pl[i]; pl[i] = pl[j]; pl[j] = u; }, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);
-                    WAVE_SYNC();
-                    continue;
-                }
-                WAVE_SYNC();   // the previous contig's keys have been read
-                for (int i = lane; i < n; i += 64) { const int a = pl[b0 + i]; sidx[i] = a; spos[i] = R.pos[c_lo + a]; }
-                WAVE_SYNC();
-                int tie = 0;
-                for (int e = lane; e < n; e += 64) {
-                    const i64 key = spos[e];
-                    int rank = 0;
-                    for (int j = 0; j < n; ++j) { const i64 kj = spos[j]; rank += kj < key; tie |= (kj == key) & (j != e); }
-                    pl[b0 + rank] = sidx[e];
-                }
-                if (__any(tie)) {
-                    // (r05: two reads drawn on one 300-bp family at the same offset have equal positions on EVERY copy — most of a repeat barcode's larger contigs have a tie.
-                    // Go's algorithm then, with the ranges of its quickSort spread over the lanes, on the keys in LDS; it was one lane's)
-#ifdef LH_RA_HIST
-                    if (lane == 0) atomicAdd(&lh_rfa_hist2[5], 1ull);
-#endif
-                    WAVE_SYNC();
-                    if (lane == 0) { shi[6] = 0; shi[7] = n; }
-                    WAVE_SYNC();
-                    wave_gosort(1, shi + 6, [&](int i, int j) { return spos[i] < spos[j]; },
-                                [&](int i, int j) { i64 t = spos[i]; spos[i] = spos[j]; spos[j] = t; int u = sidx[i]; sidx[i] = sidx[j]; sidx[j] = u; }, T.molraw, T.rdl, T.firstf, T.molc, T.ppos);
-                    WAVE_SYNC();
-                    for (int e = lane; e < n; e += 64) pl[b0 + e] = sidx[e];
-                }
-            }
-        }
-        WAVE_SYNC();
+        { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, 0, ncont, NCf, 0, 0}; rfa_sort_positions<SMALL>(R, T, B, lane, lds_raw, shi RFA_PROF_ARG); }
         RFA_PROF(4)
         RFA_FENCE()
         int do_rfa = bc_do_rfa[bc] != 0;
         int M = 0;
         if (do_rfa) {
-            for (int a = lane; a < NC; a += 64) { T.molc[a] = -1; T.ppos[a] = -1; }
-            WAVE_SYNC();
-            // ---- inferMolecules: a gap > 50 kb (or a new contig list) starts a molecule ----
-            int Mraw = 0;
-            for (int base = 0; base < NCf; base += 64) {
-                int i = base + lane, st = 0, a = -1;
-                if (i < NCf) {
-                    a = T.plist[i];
-                    st = i == T.coff[T.kidx[a]];
-                    if (!st) st = R.pos[c_lo + a] - R.pos[c_lo + T.plist[i - 1]] > 50000;
-                }
-                u64 mk = __ballot(st);
-                int mi = Mraw + __popcll(mk & ((2ull << lane) - 1)) - 1;
-                if (i < NCf) {
-                    T.molraw[i] = mi; T.molc[a] = mi; T.ppos[a] = i; T.rdl[i] = S.cand_read[c_lo + a] - r0;
-                    T.firstf[i] = -1;   // (not looked at yet: the large molecules' entries are, below, before the others)
-                    if (st) T.mstart[mi] = i;
-                }
-                Mraw += __popcll(mk);
-            }
-            if (lane == 0) T.mstart[Mraw] = NCf;
-            WAVE_SYNC();
+            int Mraw;
+            { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, 0, M}; Mraw = rfa_infer_molecules(R, S, T, B, lane); }
             RFA_PROF(16)
             RFA_FENCE()
 #ifdef LH_RA_HIST
@@ -1186,168 +1572,10 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
                 if (lane == 0) { lh_rfa_bcstat[bc & 4095][3] = Mraw; lh_rfa_bcstat[bc & 4095][4] = mxs; lh_rfa_bcstat[bc & 4095][7] = mxc; }
             }
 #endif
-            // ---- markBestAlignmentForReadInMolecule, step 1: best pair score of every entry inside its molecule; the
-            // entry's read is counted once per molecule (its first occurrence); molecules with an active alignment ----
-            // (r05) LARGE raw molecules first, from LDS.  On repeat families a read pair has a hundred alignments each within one 50-kb neighbourhood: one raw molecule of
-            // several hundred entries, in which every entry of the read is scored against every entry of its mate — n_a x n_m evaluations of ten scattered fields each,
-            // half of this kernel's time.  The molecule's entries (position, contig, strand, read, the four counts the score is made of: 24 B) are staged once and every
-            // lane scans them for ITS entry: the same set of mate entries, the same expression evaluated in the same order per pair (lariat.go:599-624 with lmp = 0: adding
-            // 0.0 to a sum that cannot be -0.0 is left out), the maximum of the same values; "first" = no earlier entry of the read in the molecule, as below.
-            {
-                struct MEnt { i64 pos; int32_t rid; uint32_t rd; int32_t s2, spare; };   // s2: twice the entry's own part of a pair's score (below)
-                static_assert(sizeof(MEnt) == 24, "24 bytes per staged entry");
-                MEnt* const me = (MEnt*)lds_raw;
-                // (r06, late) next to the records, the entries' read numbers alone, sixteen bits each: a lane looking for its mate's entries (and for earlier ones of its own
-                // read) reads EIGHT of them per round trip to LDS and fetches a 24-byte record only where the low sixteen bits match — one entry in ten on repeat families, where
-                // the scan of whole records, a dependent LDS read per entry, was two fifths of the kernel on large barcodes
-                constexpr int ME_FIT = (LH_RFA_LDS_BYTES / 26) & ~7;
-#ifdef LH_RFA_ME_CAP   // (test builds: tiles short enough for the suite's molecules to need several)
-                constexpr int ME_CAP = (LH_RFA_ME_CAP < ME_FIT ? LH_RFA_ME_CAP : ME_FIT) & ~7;
-#else
-                constexpr int ME_CAP = ME_FIT;
-#endif
-                static_assert(ME_CAP >= 8 && ME_CAP % 8 == 0 && ME_CAP * 26 <= LH_RFA_LDS_BYTES, "records and read numbers of a tile share lds_raw");
-                uint16_t* const mrd = (uint16_t*)(lds_raw + ME_CAP * 24);   // (16-byte aligned: ME_CAP is a multiple of 8)
-                auto load_ent = [&](int i) {
-                    const i64 ca = c_lo + T.plist[i];
-                    MEnt e;
-                    e.pos = R.pos[ca]; e.rid = R.rid[ca]; e.rd = (uint32_t)T.rdl[i] | (uint32_t)(R.reversed[ca] != 0) << 31;
-                    const int sc = R.soft_clipped[ca];
-                    e.s2 = R.mismatches[ca] * -4 + R.indels[ca] * -6 - (sc > 0 ? 10 * sc + R.soft_clipped_length[ca] : 0);   // twice (-2 mm - 3 id - 5 sc - 0.5 scl)
-                    e.spare = 0;
-                    return e;
-                };
-                // (r06) EVERY molecule's entries go through LDS, not only the large ones: the entries of a barcode are cut into tiles of whole molecules (they are contiguous
-                // in position order), a tile is staged once and every lane scans ITS entry's molecule inside it — a handful to a few dozen LDS records where it was as many
-                // dependent reads of ten scattered fields from memory per entry (46 % of the kernel on repeat families, 37 % on 1,000-pair barcodes with a twentieth of their
-                // pairs on them).  A molecule longer than a tile goes through tiles of its own, as in r05.
-                // (r06, late) a pair's score (lariat.go:599-624 with lmp = 0) is the sum of the two entries' own parts — whole and half numbers (-2 per mismatch, -3 per indel,
-                // -5 per clipped end, -0.5 per clipped base), every partial sum exact in a double whatever the order — plus the improper-pair penalty as the LAST addition
-                // when the pair is not proper.  So the largest score over a set of mates is max(half the largest integer sum over the proper ones, half the largest over the
-                // improper ones + penalty) — the same doubles the expression as written yields (x -> x / 2 + penalty does not decrease in x) — and the loop over the mates is
-                // integer work: it was thirty double-precision operations a pair, most of this step on repeat families.
-                auto pair_proper = [&](const MEnt& A, int arev, const MEnt& B) {
-                    int pr = 0;
-                    if (arev != (int)(B.rd >> 31) && A.rid == B.rid) { const i64 dist = arev ? A.pos - B.pos : B.pos - A.pos; pr = dist >= -35 && dist < 750; }
-                    return pr;
-                };
-                constexpr int S2_NONE = -(1 << 30);
-                auto best_of = [&](int bp, int bi) {
-                    double best = -1.7976931348623157e308;
-                    if (bp != S2_NONE) best = (double)bp * 0.5;
-                    if (bi != S2_NONE) { const double x = (double)bi * 0.5 + improper; if (x > best) best = x; }
-                    return best;
-                };
-                // entries [j0, j1) of the staged tile against entry A (read lr, mate lrm); the tile's entry j is the molecule's entry jb + j, A is its entry e
-                auto scan_tile = [&](const MEnt& A, int lr, int lrm, int arev, int j0, int j1, int jb, int e, int& bp, int& bi, int& first) {
-                    const uint32_t km = (uint32_t)lrm & 0xffffu, ko = (uint32_t)lr & 0xffffu;
-                    for (int j8 = j0 & ~7; j8 < j1; j8 += 8) {
-                        const u64* const wp = (const u64*)(mrd + j8);
-                        const u64 ww[2] = {wp[0], wp[1]};
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) {
-                            const uint32_t id = (uint32_t)(ww[u >> 2] >> ((u & 3) * 16)) & 0xffffu;
-                            const int j = j8 + u;
-                            if ((id == km || id == ko) && j >= j0 && j < j1) {
-                                const MEnt B = me[j];
-                                const int lj = (int)(B.rd & 0x7fffffffu);
-                                if (lj == lrm) {
-                                    const int s2 = A.s2 + B.s2;
-                                    if (pair_proper(A, arev, B)) bp = bp > s2 ? bp : s2;
-                                    else bi = bi > s2 ? bi : s2;
-                                } else if (lj == lr && jb + j < e) first = 0;
-                            }
-                        }
-                    }
-                };
-                for (int i0 = 0; i0 < NCf;) {
-                    const int m0 = T.molraw[i0];
-                    const int msz = T.mstart[m0 + 1] - i0;   // (i0 is the first entry of molecule m0)
-                    if (msz > ME_CAP) {
-                        // a molecule longer than the buffer goes through it in tiles: every entry keeps its maximum so far in sval, "a mate's entry seen" in psum (free until
-                        // the counting below) and "first" in firstf
-                        const int ms0 = i0;
-                        for (int t0 = 0; t0 < msz; t0 += ME_CAP) {
-                            const int tn = msz - t0 < ME_CAP ? msz - t0 : ME_CAP;
-                            WAVE_SYNC();   // the previous tile's entries have been read
-                            for (int j = lane; j < tn; j += 64) { const MEnt E = load_ent(ms0 + t0 + j); me[j] = E; mrd[j] = (uint16_t)(E.rd & 0xffffu); }
-                            WAVE_SYNC();
-                            for (int e0 = 0; e0 < msz; e0 += 64) {
-                                const int e = e0 + lane;
-                                if (e < msz) {
-                                    const int i = ms0 + e;
-                                    const MEnt A = (e >= t0 && e < t0 + tn) ? me[e - t0] : load_ent(i);
-                                    const int lr = (int)(A.rd & 0x7fffffffu), lrm = lr ^ 1, arev = (int)(A.rd >> 31);
-                                    double best = -1.7976931348623157e308;
-                                    int found = 0, first = 1, bp = S2_NONE, bi = S2_NONE;
-                                    if (t0 > 0) { best = T.sval[i]; found = T.psum[i]; first = T.firstf[i]; }
-                                    scan_tile(A, lr, lrm, arev, 0, tn, t0, e, bp, bi, first);
-                                    if (bp != S2_NONE || bi != S2_NONE) { found = 1; const double x = best_of(bp, bi); if (x > best) best = x; }
-                                    if (t0 + tn >= msz) { T.sval[i] = found ? best : R.lap[c_lo + T.plist[i]]; T.firstf[i] = first; }
-                                    else { T.sval[i] = best; T.psum[i] = found; T.firstf[i] = first; }
-                                }
-                            }
-                        }
-                        i0 += msz;
-                        continue;
-                    }
-                    // whole molecules from i0 on: up to the start of the molecule that holds entry i0 + ME_CAP
-                    int i1 = NCf;
-                    if (i0 + ME_CAP < NCf) i1 = T.mstart[T.molraw[i0 + ME_CAP]];
-                    const int tn = i1 - i0;
-                    WAVE_SYNC();   // the previous tile's entries have been read
-                    for (int j = lane; j < tn; j += 64) { const MEnt E = load_ent(i0 + j); me[j] = E; mrd[j] = (uint16_t)(E.rd & 0xffffu); }
-                    WAVE_SYNC();
-                    RFA_PROF(17)
-                    for (int e0 = 0; e0 < tn; e0 += 64) {
-                        const int e = e0 + lane;
-                        if (e < tn) {
-                            const int i = i0 + e, m = T.molraw[i];
-                            const int j0 = T.mstart[m] - i0, j1 = T.mstart[m + 1] - i0;
-                            const MEnt A = me[e];
-                            const int lr = (int)(A.rd & 0x7fffffffu), lrm = lr ^ 1, arev = (int)(A.rd >> 31);
-                            int first = 1, bp = S2_NONE, bi = S2_NONE;
-                            scan_tile(A, lr, lrm, arev, j0, j1, 0, e, bp, bi, first);
-                            T.sval[i] = bp != S2_NONE || bi != S2_NONE ? best_of(bp, bi) : R.lap[c_lo + T.plist[i]];
-                            T.firstf[i] = first;
-                        }
-                    }
-                    RFA_PROF(18)
-                    i0 = i1;
-                }
-                WAVE_SYNC();
-            }
-            int nfirst = 0, nactive = 0;
-            for (int base = 0; base < NCf; base += 64) {
-                int i = base + lane, first = 0, isact = 0;
-                const int pre = i < NCf ? T.firstf[i] : -1;
-                if (i < NCf && pre >= 0) { first = pre; isact = S.active[c_lo + T.plist[i]] != 0; }
-                u64 mf = __ballot(first), ma = __ballot(isact);
-                if (i < NCf) { T.psum[i] = nfirst + lanes_below(mf, lane); T.actc[i] = nactive + lanes_below(ma, lane); }
-                nfirst += __popcll(mf); nactive += __popcll(ma);
-            }
-            if (lane == 0) { T.psum[NCf] = nfirst; T.actc[NCf] = nactive; }
-            WAVE_SYNC();
+            { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, 0, M}; rfa_mark_best_step1(R, S, T, B, lane, improper, lds_raw RFA_PROF_ARG); }
             RFA_PROF(5)
             RFA_FENCE()
-            // ---- scrapMolecules: keep molecules with an active alignment, renumber ----
-            int ao = 0;
-            for (int base = 0; base < Mraw; base += 64) {
-                int m = base + lane;
-                int keep = m < Mraw && T.actc[T.mstart[m + 1]] - T.actc[T.mstart[m]] > 0;
-                int nr = keep ? T.psum[T.mstart[m + 1]] - T.psum[T.mstart[m]] : 0;
-                u64 mk = __ballot(keep);
-                int id = M + lanes_below(mk, lane);
-                int inc = wave_scan_add_i32(nr);
-                if (keep) {
-                    T.newid[m] = id; T.seg0[id] = T.mstart[m]; T.seg1[id] = T.mstart[m + 1];
-                    if (!SMALL || id < LH_RFA_SM_M) { H.nbest[id] = nr; H.aoff[id] = ao + inc - nr; H.alen[id] = 0; }   // (small: the on-chip tables end at LH_RFA_SM_M; more molecules: turned away below)
-                }
-                else if (m < Mraw) T.newid[m] = -1;
-                M += __popcll(mk);
-                ao += wave_readlane(inc, 63);
-            }
-            WAVE_SYNC();
+            { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, Mraw, M}; M = rfa_scrap_molecules<SMALL>(T, H, B, lane); }
             if (SMALL && M > LH_RFA_SM_M) RFA_OVERFLOW()   // more molecules than the on-chip tables hold: the regular instance takes the barcode from the start
             if ((size_t)M * (size_t)nR > best_cap) RFA_OVERFLOW()   // molecule table does not fit the slab
             for (size_t x = lane; x < (size_t)M * nR; x += 64) T.bestT[x] = -1;
@@ -1600,132 +1828,15 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa(DIndex ix, DOpts o, in
         // ---- calculateLogMoleculePenalty (lariat.go:1061-1086) ----
         // Every term of dnaLength is an integer-valued double far below 2^53, so the sum is exact in any order: the lanes share a
         // molecule's alignments (it was one lane walking all of them, 16 % of the kernel's time), the wave adds up.
-        {
-            double part = 0.0;
-            if (do_rfa && M > 0) {
-                for (int m = 0; m < M; ++m) {
-                    const int al = H.alen[m], ao = H.aoff[m];
-                    if (H.mflag[m]) {
-                        i64 smallest = 0x7fffffffffffffffll, biggest = -1;
-                        for (int k = lane; k < al; k += 64) {
-                            i64 p = R.pos[c_lo + H.act_store[ao + k]];
-                            if (p > biggest) biggest = p;
-                            if (p < smallest) smallest = p;
-                        }
-                        for (int msk = 32; msk >= 1; msk >>= 1) {
-                            const i64 ob = shfl_xor_i64(biggest, msk), os = shfl_xor_i64(smallest, msk);
-                            if (ob > biggest) biggest = ob;
-                            if (os < smallest) smallest = os;
-                        }
-                        if (lane == 0 && biggest >= smallest) part += (double)(biggest - smallest) + 1000.0;
-                    } else {
-                        for (int k = lane; k < al; k += 64) {
-                            i64 g = c_lo + H.act_store[ao + k];
-                            part += (double)(R.aend[g] - R.pos[g]) * 2.0;
-                        }
-                    }
-                }
-            }
-            for (int msk = 32; msk >= 1; msk >>= 1) part += __shfl_xor(part, msk);
-            if (lane == 0) shd[0] = (do_rfa && M > 0) ? log10((1000.0 + part) / o.genome_length * 0.05) : 0.0;
-        }
-        WAVE_SYNC();
-        double lmp = shd[0];
+        double lmp;
+        { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, 0, M}; lmp = rfa_molecule_penalty(R, H, B, lane, shd, o.genome_length); }
         RFA_PROF(9)
         RFA_FENCE()
-        // ---- per read: link active mates (lariat.go:892-900).  Done for all reads before any scoring that reads mate links. ----
-        for (int r = lane; r < nR; r += 64) {
-            i64 act = -1;
-            for (i64 a = R.cand_off[r0 + r]; a < R.cand_off[r0 + r + 1]; ++a) if (R.in_filtered[a] && S.active[a]) act = a;
-            S.active_idx[r0 + r] = act;
-        }
-        WAVE_SYNC();
-        for (int r = lane; r < nR; r += 64) {
-            i64 a = S.active_idx[r0 + r], m = S.active_idx[r0 + (r ^ 1)];
-            S.mate[a] = m;
-        }
-        WAVE_SYNC();
-        // ---- estimateMapQualities per read (lariat.go:887-990).  A read with few (alignment, mate alignment) combinations: one lane; the others
-        // (a read on a repeat family and its mate: thousands) are listed and done by the whole wave below, a lane per alignment ----
-        // the reads with many combinations: listed for k_rfa_mq_w (with the barcode, whose molecule penalty they need)
-        if (lane == 0) bc_lmp[bc] = lmp;
-        for (int rb_ = 0; rb_ < nR; rb_ += 64) {
-            const int r = rb_ + lane;
-            int hv = 0;
-            if (r < nR) hv = (R.cand_off[r0 + r + 1] - R.cand_off[r0 + r]) * (R.cand_off[r0 + (r ^ 1) + 1] - R.cand_off[r0 + (r ^ 1)]) > LH_RFA_MAPQ_WAVE;
-            const u64 mh = __ballot(hv);
-            if (mh) {
-                int basep = 0;
-                if (lane == 0) basep = atomicAdd(hr_count, (int32_t)__popcll(mh));
-                basep = wave_readlane(basep, 0);
-                if (hv) { const int at = basep + lanes_below(mh, lane); hr_list[2 * at] = r0 + r; hr_list[2 * at + 1] = bc; }
-            }
-        }
-        WAVE_SYNC();
+        { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, 0, M}; rfa_link_mates(R, S, B, lane); }
+        { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, 0, M}; rfa_list_heavy_reads(R, B, lane, lmp, bc_lmp, hr_list, hr_count); }
         RFA_PROF(10)
         RFA_FENCE()
-        for (int r = lane; r < nR; r += 64) {
-            int gr = r0 + r, gm = r0 + (r ^ 1);
-            i64 a0 = R.cand_off[gr], a1 = R.cand_off[gr + 1], m0 = R.cand_off[gm], m1 = R.cand_off[gm + 1];
-            if ((a1 - a0) * (m1 - m0) > LH_RFA_MAPQ_WAVE) continue;
-            double* const top = (double*)lds_raw;   // the read's 15 best scores, lane-strided in LDS (the phases that staged things there are over): no scratch
-#define TOPV(k_) top[(k_) * 64 + lane]
-            int ntop = 0;
-#define TOP_PUSH(v_)                                                                   \
-    {                                                                                  \
-        double v = (v_);                                                               \
-        int k_ = ntop < LH_MAPQ_TOP ? ntop : LH_MAPQ_TOP;                              \
-        if (ntop < LH_MAPQ_TOP || v > TOPV(LH_MAPQ_TOP - 1)) {                         \
-            if (ntop < LH_MAPQ_TOP) ntop++; else k_ = LH_MAPQ_TOP - 1;                 \
-            while (k_ > 0 && TOPV(k_ - 1) < v) { TOPV(k_) = TOPV(k_ - 1); k_--; }      \
-            TOPV(k_) = v;                                                              \
-        }                                                                              \
-    }
-            // pseudo-count entry (appendPsuedocountAlignmentScore): first filtered alignment of the read + best single mate
-            i64 first = -1;
-            for (i64 a = a0; a < a1; ++a) if (R.in_filtered[a]) { first = a; break; }
-            double bestSingle = -1.7976931348623157e308;
-            for (i64 m = m0; m < m1; ++m) {
-                if (!R.in_filtered[m]) continue;
-                double s = dev_score_aln(R, S, improper, -1, m, lmp);
-                if (s > bestSingle) bestSingle = s;
-            }
-            double pseudo = bestSingle + dev_pseudo_score(R, first, lmp);
-            TOP_PUSH(pseudo)
-            for (i64 a = a0; a < a1; ++a) {   // best pair score of every alignment
-                if (!R.in_filtered[a]) continue;
-                double best = -1.7976931348623157e308;
-                for (i64 m = m0; m < m1; ++m) {
-                    if (!R.in_filtered[m]) continue;
-                    double s = dev_score_aln(R, S, improper, a, m, lmp);
-                    if (s > best) best = s;
-                }
-                TOP_PUSH(best)
-            }
-            // second best (lariat.go:917-943); sets mate_alignment of the inactive alignment it selects
-            double sb_raw = pseudo, sb_lp = -1000.0;
-            i64 sb_aln = -1;
-            for (i64 a = a0; a < a1; ++a) {
-                if (!R.in_filtered[a] || S.active[a]) continue;
-                for (i64 m = m0; m < m1; ++m) {
-                    if (!R.in_filtered[m]) continue;
-                    double s = dev_score_aln(R, S, improper, a, m, lmp);
-                    if (s > sb_lp) { sb_lp = s; sb_raw = dev_score_aln(R, S, improper, a, m, 0.0); sb_aln = a; S.mate[a] = m; }
-                }
-            }
-            i64 act = S.active_idx[gr];
-            S.second_best_idx[gr] = sb_aln; S.second_best_score[gr] = sb_raw;
-            S.as_score[gr] = dev_score_aln(R, S, improper, act, S.mate[act], 0.0);
-            double total = 0;
-            for (int k = 0; k < ntop; ++k) total += dev_mapq_pow10(TOPV(k));
-            for (i64 a = a0; a < a1; ++a) {
-                if (!R.in_filtered[a]) continue;
-                S.mapq[a] = dev_mapq(dev_score_aln(R, S, improper, a, S.mate[a], lmp), total, S.sum_move[a], dev_in_centromere(R, cen_start, cen_end, a));
-            }
-#undef TOP_PUSH
-#undef TOPV
-        }
-        WAVE_SYNC();
+        { const RfaBc B = {bc, r0, nR, NC, c_lo, ncmax, best_cap, do_rfa, ncont, NCf, 0, M}; rfa_mapq_lane(R, S, B, lane, improper, lmp, cen_start, cen_end, lds_raw); }
         RFA_PROF(11)
         RFA_FENCE()
 #ifdef LH_RA_HIST
@@ -1906,10 +2017,8 @@ __global__ void __launch_bounds__(64, LH_RFA_WAVES) k_rfa_post(DIndex ix, DOpts 
         while ((1 << hbits) < 2 * nR) ++hbits;
         size_t so = 0;
         RfaTab T;
-#define CARVE(ptr, type, count) { so = (so + 7) & ~(size_t)7; T.ptr = (type*)(slab + so); so += sizeof(type) * (size_t)(count); }
-        CARVE(dk0, u64, nR) CARVE(dk1, u64, nR) CARVE(dk2, u64, nR) CARVE(dk3, u64, nR) CARVE(htab, int32_t, (size_t)1 << hbits)
-        CARVE(gstk, int32_t, 3 * LH_GOSORT_STK * 64) CARVE(spl, i64, LH_SPLIT_MAX * 64)
-#undef CARVE
+        LH_RFA_CARVE(dk0, u64, nR) LH_RFA_CARVE(dk1, u64, nR) LH_RFA_CARVE(dk2, u64, nR) LH_RFA_CARVE(dk3, u64, nR) LH_RFA_CARVE(htab, int32_t, (size_t)1 << hbits)
+        LH_RFA_CARVE(gstk, int32_t, 3 * LH_GOSORT_STK * 64) LH_RFA_CARVE(spl, i64, LH_SPLIT_MAX * 64)
         if (so > (size_t)slab_bytes) RFA_OVERFLOW()   // barcode too large for the slab
         // ---- markDuplicates: first-seen wins on (read1?, reversed, contig, pos, mate contig, mate pos) in read order ----
         {   // open-addressing table over the keys; a slot ends up holding the smallest read index of its key
